@@ -2,9 +2,18 @@
 """Benchmark: simplex iterations/sec of the MI355X engine on BASELINE.json's
 north-star workload, config 5 (synthetic sparse LP 100k x 1M, 0.01% dense,
 dual simplex with dual steepest edge, 1 MI355X), with the dominant kernel's
-roofline and the CPU oracle (Glop restatement) timed on the host in the same
-run. Config 2 (dense 10k x 50k, primal), config 3 (Netlib-shaped suite) and
-config 4 (CP-SAT-style children) follow as extra sections of the same line.
+roofline from the timed window's own HIP events.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the
+headline needs: it sets up, warms up, times the K iterations, writes the
+solve's outputs if --dump-outputs DIR is given, and prints the result line.
+--full adds everything else to the same line: the refactorization-amortized
+config-5 window, the CPU oracle (Glop restatement) timed on the host on the
+same LP and its bit-for-bit check of the engine's final state, and the
+config 2 (dense 10k x 50k, primal), config 3 (Netlib-shaped suite) and
+config 4 (CP-SAT-style children) sections with their own CPU baselines,
+oracle checks and rooflines. The section switches (--no-c5, --no-c2, --no-c3,
+--batch-lps 0, --no-cpu) choose among what --full runs.
 
 A "step" is one simplex iteration (RevisedSimplex::DualMinimize loop body,
 revised_simplex.cc:3058-3367) at iteration 20 000 of the solve (--c5-window):
@@ -133,6 +142,44 @@ def window_stats(ts, start, done, before, after):
     return out
 
 
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # --dump-outputs writes less than 64 MB in all
+
+
+def solution_arrays(h, r):
+    """What a caller of the solve receives (include/mi_lp.h getters) after
+    mi_lp_finish, by name, for --dump-outputs."""
+    var, cons = h.statuses()
+    return {"result": np.array([r.iterations, r.problem_status, r.error_code, r.objective],
+                               dtype=np.float64),
+            "primal": h.primal(), "duals": h.duals(), "reduced_costs": h.reduced_costs(),
+            "activities": h.activities(), "basis": h.basis(), "state": h.state(),
+            "var_status": var, "cons_status": cons}
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes each array as out_dir/<name>.npy: float64 stays float64, 32-bit
+    integers become float64 (exact), 8-bit statuses float32 (exact). Outputs
+    larger than DUMP_LIMIT_BYTES in all are cut to a fixed, seeded sample of
+    every array (the same indices on every run with the same sizes)."""
+    os.makedirs(out_dir, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float32 if a.dtype.itemsize == 1
+                                          else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(20261015)
+        frac = DUMP_LIMIT_BYTES / total
+        for name, a in conv.items():
+            keep = np.sort(rng.choice(a.size, max(1, int(a.size * frac)), replace=False))
+            conv[name] = a[keep]
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"outputs: {len(conv)} arrays, {sum(a.nbytes for a in conv.values()) / 1e6:.1f} MB "
+        f"written to {out_dir}")
+
+
 def kernel_table(stats):
     return {k: {"launches": v["launches"], "device_ms": round(v["device_ms"], 3),
                 "call_ms": round(v["call_ms"], 3), "GB": round(v["bytes"] / 1e9, 4)}
@@ -143,14 +190,17 @@ def run_c5(args, rank, world, local_rank, dist, barrier, sync):
     """Config 5: synthetic sparse LP 100k x 1M, 0.01% nnz,
     dual simplex with dual steepest edge. One LP per rank (replicas, seed +
     rank). The solve runs untimed to iteration c5_window + warmup; then
-    exactly `steps` iterations are timed with the kernel timing on."""
+    exactly `steps` iterations are timed with the kernel timing on. A plain
+    run caps the solve there and finishes it; --full continues the window to
+    c5_amortized iterations and runs the CPU oracle on the same LP."""
     import lp_gen
     split = world > 1 and args.c5_split
     lp = lp_gen.sparse_c5_lp(args.c5_m, args.c5_n, 10, args.seed + (0 if split else rank))
     start = args.c5_window + args.warmup
     # The solve is capped where the timed windows end, so that its final
-    # state is the one the oracle reaches with the same cap (oracle_check).
-    end = start + max(args.steps, args.c5_amortized)
+    # state is the one the oracle reaches with the same cap (oracle_check)
+    # and the one --dump-outputs writes.
+    end = start + (max(args.steps, args.c5_amortized) if args.full else args.steps)
     p = abi.default_params(use_dual_simplex=1, max_number_of_iterations=end)
     h = engine.LpHandle(p, device=local_rank)
     if split:
@@ -199,7 +249,9 @@ def run_c5(args, rank, world, local_rank, dist, barrier, sync):
     # so a short --steps window cannot hide the LU refactorizations.
     amortized = None
     span = max(args.c5_amortized, done)
-    if not fin and span > done:
+    if not args.full:
+        amortized = None  # a plain run times the headline window only
+    elif not fin and span > done:
         before_a = h.run_counters()
         barrier()
         sync()
@@ -220,10 +272,12 @@ def run_c5(args, rank, world, local_rank, dist, barrier, sync):
                      if elapsed > 0 else 0.0, "ms_per_step": 1000.0 * elapsed / max(1, done),
                      "window": window}
     # Run on to the cap (untimed): the final state is compared with the
-    # oracle's at the same iteration below.
+    # oracle's at the same iteration below (--full).
     h.run_until(end + 1)
     final = h.finish()
-    digests = _solution_digests(h, final) if rank == 0 and world == 1 else None
+    oracle = args.full and rank == 0 and world == 1 and not args.no_cpu
+    digests = _solution_digests(h, final) if oracle else None
+    outputs = solution_arrays(h, final) if args.dump_outputs and rank == 0 else None
     del h
     out = {
         "value": total_done / elapsed if elapsed > 0 else 0.0,
@@ -241,6 +295,7 @@ def run_c5(args, rank, world, local_rank, dist, barrier, sync):
         "amortized": amortized,
         "split": split,
         "event_timed_kernels": timed or "all",
+        "outputs": outputs,
     }
     if split:
         ex = stats.get("exchange", {})
@@ -248,7 +303,7 @@ def run_c5(args, rank, world, local_rank, dist, barrier, sync):
                            "allgathers_per_step": ex.get("launches", 0) / max(1, done),
                            "us_per_step": 1000.0 * ex.get("call_ms", 0.0) / max(1, done),
                            "bytes_per_step": ex.get("bytes", 0.0) / max(1, done)}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if oracle:
         import oracle_lib
         # The oracle runs the same solve with the same cap; its per-iteration
         # timestamps give its rate on exactly the GPU's headline window and
@@ -707,14 +762,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=20,
                     help="untimed config-5 iterations after --c5-window")
     ap.add_argument("--seed", type=int, default=20261015)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline window: the config-5 "
+                         "amortized window, the CPU oracle baselines and checks, and the "
+                         "config 2, 3 and 4 sections (the switches below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the config-5 solve returns "
+                         "at its last timed iteration (with --full: at the end of the "
+                         "amortized window) as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--c5-m", type=int, default=100000)
     ap.add_argument("--c5-n", type=int, default=1000000)
     ap.add_argument("--c5-window", type=int, default=20000,
                     help="config-5 iteration where the timed window starts")
     ap.add_argument("--c5-amortized", type=int, default=1000,
-                    help="config-5 iterations of the refactorization-amortized window "
-                         "(starts with the headline window)")
+                    help="--full: config-5 iterations of the refactorization-amortized "
+                         "window (starts with the headline window)")
     ap.add_argument("--c5-timed-kernels", default="tri_solve,tri_solve_tau",
                     help="kernel ids bracketed with HIP events in the config-5 windows "
                          "(comma-separated, or 'all')")
@@ -778,6 +841,11 @@ def main():
         args.cpu_iters = args.c2_steps
     if args.cpu_warmup is None:
         args.cpu_warmup = args.c2_warmup
+    if not args.full:  # a plain run: the config-5 headline window alone
+        if args.no_c5:
+            ap.error("--no-c5 leaves a plain run nothing to do: the other sections need --full")
+        args.no_cpu = args.no_c2 = args.no_c3 = True
+        args.batch_lps = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks (one process
@@ -828,7 +896,8 @@ def main():
         c5 = {"value": 0.0, "ms_per_step": 0.0, "timed_iterations": [0, 0], "finished_early": False,
               "setup_and_warmup_s": 0.0, "nnz": 0, "roofline": None, "kernels": {},
               "event_timed_kernels": None, "host_ms_per_step": None,
-              "device_call_ms_per_step": None, "window": None, "split": False}
+              "device_call_ms_per_step": None, "window": None, "split": False,
+              "outputs": None}
     else:
         log(f"config-5 headline: {args.c5_m}x{args.c5_n}")
         c5 = run_c5(args, rank, world, local_rank, dist, barrier, sync)
@@ -850,6 +919,11 @@ def main():
         log(f"batched: {batched['value']:.1f} LPs/s")
     if rank != 0:
         return
+    if args.dump_outputs:
+        if c5["outputs"] is None:
+            log("outputs: nothing to write (--no-c5)")
+        else:
+            dump_outputs(args.dump_outputs, c5["outputs"])
     line = {
         "metric": METRIC,
         "value": c5["value"],
@@ -857,6 +931,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": c5["ms_per_step"],
         "higher_is_better": True,
         "scaling": "strong" if c5["split"] else "weak",

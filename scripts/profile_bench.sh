@@ -2,7 +2,7 @@
 # rocprofv3 passes of one bench.py command, each its own run (kernel trace
 # with --stats, FETCH_SIZE, WRITE_SIZE: the TCC slots cannot hold both),
 # summarised into profiles/<tag>/ by scripts/profile_summary.py.
-#   scripts/profile_bench.sh <tag> <c2|c3|c4|c5> <bench.py arguments...>
+#   scripts/profile_bench.sh <tag> <c2|c3|c4|c5> <bench.py arguments after --full...>
 # For c3/c4 set PROFILE_LPS to the LPs the profiled process solves (bench.py
 # --profile-batch prints it): the traffic is then also given per LP.
 # Runs from the repo root on the GPU box; a failing pass ends the script.
@@ -28,10 +28,10 @@ export MILP_DEVICE_RESET_AT_EXIT=1 MILP_CRASH_REPORT=1
 cleanup() { rm -f $OUT/trace/run_kernel_trace.csv $OUT/*/run_counter_collection.csv $OUT/*/*.db; }
 trap cleanup EXIT
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
-  python3 $R/bench.py "$@" ${TRACE_EXTRA:-} > $OUT/trace.log 2>&1 || { echo "trace pass failed"; exit 1; }
+  python3 $R/bench.py --full "$@" ${TRACE_EXTRA:-} > $OUT/trace.log 2>&1 || { echo "trace pass failed"; exit 1; }
 for c in FETCH_SIZE WRITE_SIZE; do
   p=$(echo $c | tr A-Z a-z | cut -d_ -f1)
   timeout -k 10 600 rocprofv3 --pmc $c -d $OUT/$p -o run --output-format csv -- \
-    python3 $R/bench.py "$@" > $OUT/$p.log 2>&1 || { echo "$c pass failed"; exit 1; }
+    python3 $R/bench.py --full "$@" > $OUT/$p.log 2>&1 || { echo "$c pass failed"; exit 1; }
 done
 cd $R && PROFILE_OUT_ROOT=$R/gpurun_out/profiles python3 scripts/profile_summary.py $OUT $tag $workload ${PROFILE_LPS:-0}

@@ -1,6 +1,6 @@
 set -u
 cd $GRAFT_REPO_ROOT
-B="python3 -u bench.py --no-c5 --no-c2 --batch-lps 0 --no-cpu --profile-batch"
+B="python3 -u bench.py --full --no-c5 --no-c2 --batch-lps 0 --no-cpu --profile-batch"
 scripts/gpu_run.sh gpurun_out/r06_j \
  "base@200=$B" \
  "hpool@200=MILP_BATCH_HOST_POOL=1 $B" \

@@ -1,7 +1,7 @@
 set -u
 cd $GRAFT_REPO_ROOT
 T="python3 -u -m pytest -x -v -s --timeout 300 --timeout-method thread -p no:cacheprovider"
-B="python3 -u bench.py --no-c5 --no-c2 --no-c3 --no-cpu --batch-share-lps 0"
+B="python3 -u bench.py --full --no-c5 --no-c2 --no-c3 --no-cpu --batch-share-lps 0"
 scripts/gpu_run.sh gpurun_out/r06_n \
  "tests@600=$T tests/test_batch_policy_gpu.py tests/test_sdual_gpu.py tests/test_independent_gpu.py tests/test_comm_gpu.py" \
  "t0@200=MILP_SDUAL_TAIL=0 $B" \

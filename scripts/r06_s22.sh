@@ -7,5 +7,5 @@ steps+=("ts@200=MILP_TIGHTEN_STATS=1 $C5")
 for r in 1 2 3; do
   steps+=("new$r@200=$C5" "old$r@200=MILP_DUAL_TIGHTEN_SORT=1 $C5")
 done
-steps+=("bench@400=python3 -u bench.py --no-c2 --no-c3 --batch-lps 0 --batch-share-lps 0 --steps 20 --warmup 5")
+steps+=("bench@400=python3 -u bench.py --full --no-c2 --no-c3 --batch-lps 0 --batch-share-lps 0 --steps 20 --warmup 5")
 scripts/gpu_run.sh gpurun_out/r06_v "${steps[@]}"

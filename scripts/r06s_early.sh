@@ -6,7 +6,7 @@ bash scripts/gpu_run.sh "$out" \
   "spec@300=$T tests/test_device_solve_gpu.py -k 'early or speculative or async_tau'" \
   "dual@400=$T tests/test_parity_gpu.py -k 'device_dual or async_tau or mps'" \
   "split@300=$T tests/test_split_gpu.py tests/test_shards_gpu.py" \
-  "c5on@330=python -u bench.py --no-c2 --no-c3 --batch-lps 0" \
-  "c5off@200=MILP_EARLY_FLIPS=0 python -u bench.py --no-c2 --no-c3 --batch-lps 0 --no-cpu" \
-  "c5on2@200=python -u bench.py --no-c2 --no-c3 --batch-lps 0 --no-cpu" \
-  "c5off2@200=MILP_EARLY_FLIPS=0 python -u bench.py --no-c2 --no-c3 --batch-lps 0 --no-cpu"
+  "c5on@330=python -u bench.py --full --no-c2 --no-c3 --batch-lps 0" \
+  "c5off@200=MILP_EARLY_FLIPS=0 python -u bench.py --full --no-c2 --no-c3 --batch-lps 0 --no-cpu" \
+  "c5on2@200=python -u bench.py --full --no-c2 --no-c3 --batch-lps 0 --no-cpu" \
+  "c5off2@200=MILP_EARLY_FLIPS=0 python -u bench.py --full --no-c2 --no-c3 --batch-lps 0 --no-cpu"
