@@ -486,6 +486,23 @@ class DeviceLp : public DeviceSolver {
   // Above this many filtered rows the row-wise update row runs column by
   // column (MILP_ROWWISE_CHUNK_MAX_ROWS); both kernels give identical bits.
   int rowwise_chunk_max_rows_ = 16;
+  // Hypersparse update rows (algorithm 0 or 1) whose filtered rows hold at
+  // most this many entries go straight to their list in one workgroup
+  // (row_wise_list_kernel): no flags, no N-sized pass. Set in Init to the
+  // kernel's LDS cap; MILP_ROWWISE_LIST_MAX_ENTRIES lowers it,
+  // MILP_ROWWISE_LIST=off restores the flag kernels + Compact.
+  bool rowwise_list_enabled_ = true;
+  int rowwise_list_max_entries_ = 0;
+  // Host-known upper bound of *d_count_, set by every update-row path: the
+  // launches that consume the list are sized by it instead of N.
+  int list_bound_ = 0;
+  // The last update row came from the list kernel: d_flags_ does not describe
+  // it until FlagsFromList rebuilds it (only where a later pass reads flags).
+  bool flags_stale_ = false;
+  void FlagsFromList();
+  // Dual ratio test: lists bounded by at most this many slots run both
+  // passes in one workgroup (MILP_DUAL_RATIO_ONE_WG_MAX, 0 = never).
+  int dual_one_wg_max_ = 0;
   // Rows holding every structural column (MILP_FULL_ROWS=off disables the
   // full-row kernel).
   std::vector<uint8_t> h_row_full_;

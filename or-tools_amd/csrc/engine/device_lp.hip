@@ -143,6 +143,18 @@ void DeviceLp::Init(int device) {
   if (const char* r = std::getenv("MILP_ROWWISE_CHUNK_MAX_ROWS")) {
     rowwise_chunk_max_rows_ = std::atoi(r);
   }
+  if (const char* f = std::getenv("MILP_ROWWISE_LIST")) {
+    rowwise_list_enabled_ = std::strcmp(f, "off") != 0;
+  }
+  rowwise_list_max_entries_ = milp_kernels::kListEntriesMax;
+  if (const char* v = std::getenv("MILP_ROWWISE_LIST_MAX_ENTRIES")) {
+    rowwise_list_max_entries_ =
+        std::max(0, std::min(std::atoi(v), milp_kernels::kListEntriesMax));
+  }
+  dual_one_wg_max_ = milp_launch::kDualOneWgMax;
+  if (const char* v = std::getenv("MILP_DUAL_RATIO_ONE_WG_MAX")) {
+    dual_one_wg_max_ = std::max(0, std::min(std::atoi(v), milp_launch::kDualOneWgMax));
+  }
   if (const char* f = std::getenv("MILP_FULL_ROWS")) {
     full_rows_enabled_ = std::strcmp(f, "off") != 0;
   }
@@ -891,6 +903,7 @@ void DeviceLp::UploadMatrix(const CompactSparseMatrix& csc, const CompactSparseM
   }
   mapped_result_ = false;
   list_count_ = 0;
+  list_bound_ = n_total_;
   dual_ready_ = false;
   last_list_len_ = 0;
   ++list_epoch_;
@@ -955,6 +968,10 @@ void DeviceLp::LaunchColumnDots(int mode, const double* d_y, const double* d_c,
   a.mask = d_masks_[kRelevant];
   a.flags = d_flags_;
   a.drop_tolerance = 0.0;
+  // The list kernel leaves no flags behind: the two passes that read them
+  // (the dots parked on a pricing pass, the dense block's listed dots) get
+  // them from the list first.
+  if (flags_stale_ && (mode == 5 || (mode == 2 && nd_ > 0))) FlagsFromList();
   if (mode == 2) {  // dots over the update-row list
     a.ncols = list_count_;
     a.col_list = d_list_;
@@ -985,6 +1002,15 @@ void DeviceLp::LaunchColumnDots(int mode, const double* d_y, const double* d_c,
     d.drop_tolerance = drop_;
     Check(milp_launch::dense_dot(mode, dense_unroll_, d, S(stream_)), "dense dots");
   }
+}
+
+// d_flags_ = the indicator of d_list_[0, *d_count_), as the flag kernels and
+// Compact leave it.
+void DeviceLp::FlagsFromList() {
+  Check(hipMemsetAsync(d_flags_, 0, n_total_ * sizeof(uint8_t), S(stream_)), "memset");
+  Check(milp_launch::flags_from_list(d_list_, d_count_, list_bound_, d_flags_, S(stream_)),
+        "flags from list");
+  flags_stale_ = false;
 }
 
 void DeviceLp::SetMask(Mask which, const uint64_t* words, int num_words) {
@@ -1078,12 +1104,14 @@ void DeviceLp::Compact(int n) {
   }
   list_count_ = -1;  // known after FetchUpdateRow
   ++list_epoch_;
+  list_bound_ = n;  // the row-wise callers know better
 }
 
 void DeviceLp::UpdateRowColumnWise(const std::vector<double>& rho, double drop,
                                    int64_t relevant_entries, const std::vector<double>* w) {
   if (!shards_.empty()) return ShardedUpdateRowColumnWise(rho, drop, relevant_entries, w);
   CallTimer timer(&stats_, MI_K_UPDATE_ROW);
+  flags_stale_ = false;  // every path below writes all of d_flags_
   small_dots_mapped_ = false;
   if (small_fused_enabled_ && h_small_in_ != nullptr && !medium_ && nd_ == 0 &&
       m_ <= milp_kernels::kSmallColWiseRows) {
@@ -1166,6 +1194,7 @@ void DeviceLp::UpdateRowColumnWiseSmall(const std::vector<double>& rho, double d
   mapped_result_ = true;
   list_count_ = -1;  // known after FetchUpdateRow
   ++list_epoch_;
+  list_bound_ = n_total_;
   fused_ready_ = (w != nullptr);
   small_dots_mapped_ = (w != nullptr);
 }
@@ -1177,9 +1206,12 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
   CallTimer timer(&stats_, algorithm == 0 ? MI_K_SINGLE_ROW : MI_K_UPDATE_ROW);
   const int k = static_cast<int>(filtered_rows.size());
   fused_ready_ = false;
+  flags_stale_ = false;  // every path but the list kernel writes all of d_flags_
+  // No row-wise algorithm lists more columns than the filtered rows hold.
+  double entries = 0.0;
+  for (int r : filtered_rows) entries += double(h_t_starts_[r + 1] - h_t_starts_[r]);
+  const int bound = static_cast<int>(std::min<double>(n_total_, entries));
   if (small_fused_enabled_ && h_small_in_ != nullptr) {
-    double entries = 0.0;
-    for (int r : filtered_rows) entries += double(h_t_starts_[r + 1] - h_t_starts_[r]);
     // Few short rows: applied row by row; otherwise column by column.
     const bool serial = k <= small_serial_rows_ && k <= milp_kernels::kSmallRowsMax &&
                         entries <= milp_kernels::kSmallEntries;
@@ -1222,6 +1254,41 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
   a.drop_tolerance = drop;
   a.algorithm = algorithm;
   const int id = algorithm == 0 ? MI_K_SINGLE_ROW : MI_K_UPDATE_ROW;
+  if (rowwise_list_enabled_ && !all_full && algorithm <= 1 &&
+      k <= milp_kernels::kListRowsMax && entries <= rowwise_list_max_entries_) {
+    // Hypersparse: one workgroup merges the rows' entries straight into the
+    // list. d_flags_ is not written (FlagsFromList, where a pass reads it).
+    milp_kernels::RowWiseListArgs l{};
+    l.t_starts = d_t_starts_;
+    l.t_cols = d_t_cols_;
+    l.t_vals = d_t_vals_;
+    l.filtered_rows = d_rows;
+    l.rho = d_rho;
+    l.num_filtered = k;
+    l.relevant = d_masks_[kRelevant];
+    l.coefficient = d_coeff_;
+    l.drop_tolerance = drop;
+    l.algorithm = algorithm;
+    l.list = d_list_;
+    l.vals = d_out_list_;
+    l.count = d_count_;
+    // The mapped mirrors as Compact writes them: always for small N.
+    const bool mirror = list_mirror_ || n_total_ <= milp_launch::kSmallCompactMax;
+    l.host_list = mirror ? d_map_list_ : nullptr;
+    l.host_vals = mirror ? d_map_vals_ : nullptr;
+    l.host_count = mirror ? d_map_count_ : nullptr;
+    BeginKernel(id);
+    Check(milp_launch::row_wise_list(l, static_cast<int>(entries), S(stream_)), "rowwise list");
+    // The CSR entries, the rows and multipliers, the list slots (their count
+    // is not known here: bounded by the entries).
+    EndKernel(id, 12.0 * entries + 12.0 * k + 12.0 * bound);
+    mapped_result_ = mirror;
+    list_count_ = -1;  // known after FetchUpdateRow
+    ++list_epoch_;
+    list_bound_ = bound;
+    flags_stale_ = true;
+    return;
+  }
   BeginKernel(id);
   if (all_full) {
     // Full rows: a thread per column reads each row's entry directly.
@@ -1248,6 +1315,7 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
     // Values only (the column index of entry j is j), the list, the outputs.
     EndKernel(id, 8.0 * double(k) * (num_structural_ + 1) + 12.0 * k + 9.0 * n_total_);
     Compact(n_total_);
+    list_bound_ = bound;
     return;
   }
   if (k <= rowwise_chunk_max_rows_ || max_col_len_ > kColumnKernelMaxColumnLength) {
@@ -1275,10 +1343,9 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
     c.algorithm = algorithm;
     Check(milp_launch::row_wise_update_by_column(c, S(stream_)), "rowwise by column");
   }
-  double entries = 0.0;
-  for (int r : filtered_rows) entries += double(h_t_starts_[r + 1] - h_t_starts_[r]);
   EndKernel(id, 12.0 * entries + 12.0 * k + 9.0 * n_total_);
   Compact(n_total_);
+  list_bound_ = bound;
 }
 
 // Small LPs: inputs in mapped host memory, one launch, the list comes back in
@@ -1325,6 +1392,7 @@ void DeviceLp::UpdateRowRowWiseSmall(const std::vector<int>& filtered_rows,
     mapped_result_ = true;
     list_count_ = -1;
     ++list_epoch_;
+    list_bound_ = n_total_;
     return;
   }
   milp_kernels::RowWiseSmallArgs a{};
@@ -1354,6 +1422,7 @@ void DeviceLp::UpdateRowRowWiseSmall(const std::vector<int>& filtered_rows,
   mapped_result_ = true;
   list_count_ = -1;  // known after FetchUpdateRow
   ++list_epoch_;
+  list_bound_ = n_total_;
 }
 
 void DeviceLp::NextRowTag() {
@@ -1778,8 +1847,10 @@ void DeviceLp::CheckScan() {
 
 // Two launches: pass 1 (the bound B), then pass 2 fused with its ordered
 // compaction and the candidate gather into mapped host memory; one stream
-// synchronization, no copies. Only a large pass-2 set (rare) adds the
-// tightening round (keys, radix sort, walk, pass 2 again).
+// synchronization, no copies. Both are sized by the list's host-known bound
+// (list_bound_), and a short list takes one launch of one workgroup instead.
+// Only a large pass-2 set (rare) adds the tightening round (keys, radix
+// sort, walk, pass 2 again).
 // MILP_TIGHTEN_STATS=1: at exit, how many breakpoints the tightening passes
 // sorted (k1) and how far the walk went, by powers of two.
 struct TightenStats {
@@ -1818,7 +1889,9 @@ void DeviceLp::DualRatioCandidates(double sign, double threshold, double harris_
   a.list = d_list_;
   a.list_coeff = d_out_list_;
   a.count = d_count_;
-  a.max_count = n_total_;
+  // The launches are sized by the list's host-known bound, not by N.
+  const int bound = std::max(0, std::min(list_bound_, n_total_));
+  a.max_count = bound;
   a.rc = d_rc_;
   a.colbits = d_colbits_;
   a.bound_diff = d_bound_diff_;
@@ -1842,15 +1915,22 @@ void DeviceLp::DualRatioCandidates(double sign, double threshold, double harris_
   // copy: this one keeps its candidates on the device.
   sel.host_cap = std::max(0, tighten_min_candidates_);
   BeginKernel(MI_K_DUAL_RATIO);
-  Check(milp_launch::dual_ratio_bound(a, S(stream_)), "dual ratio bound");
-  Check(milp_launch::dual_ratio_select(a, sel, NextScan(), S(stream_)), "dual ratio select");
+  if (bound <= dual_one_wg_max_) {
+    // A short list: both passes in one workgroup, no tile chain.
+    Check(milp_launch::dual_ratio_one_wg(a, sel, S(stream_)), "dual ratio one workgroup");
+  } else {
+    Check(milp_launch::dual_ratio_bound(a, S(stream_)), "dual ratio bound");
+    Check(milp_launch::dual_ratio_select(a, sel, NextScan(), S(stream_)), "dual ratio select");
+  }
   EndKernel(MI_K_DUAL_RATIO, 0.0);  // bytes added once the list length is known
   Synchronize();
   CheckScan();
   const int k1 = h_dual_counts_[0];
   // Many breakpoints under B: tighten the bound by walking them in pop order.
   if (k1 > tighten_min_candidates_) {
-    if (k1 > n_total_) throw DeviceError("dual ratio test: bad counts");
+    if (k1 > bound || h_dual_counts_[1] > bound) {
+      throw DeviceError("dual ratio test: bad counts");
+    }
     BeginKernel(MI_K_DUAL_RATIO);
     if (tighten_sort_) {
       Check(milp_launch::dual_ratio_keys(a, d_slots_, k1, d_keys_in_, S(stream_)), "keys");
@@ -1878,7 +1958,8 @@ void DeviceLp::DualRatioCandidates(double sign, double threshold, double harris_
   }
   const int k = h_dual_counts_[0];
   const int count = h_dual_counts_[1];
-  if (k < 0 || k > n_total_ || count < 0 || count > n_total_) {
+  // A list longer than the bound the launches were sized by lost slots.
+  if (k < 0 || k > bound || count < 0 || count > bound) {
     throw DeviceError("dual ratio test: bad counts");
   }
   last_candidates_ = k;
@@ -1903,7 +1984,7 @@ void DeviceLp::DualUpdateReducedCosts(double mult, int leaving_col, double leavi
   CallTimer timer(&stats_, MI_K_RC_UPDATE);
   ++rc_epoch_;
   BeginKernel(MI_K_RC_UPDATE);
-  Check(milp_launch::update_reduced_costs(d_list_, d_out_list_, d_count_, n_total_, mult,
+  Check(milp_launch::update_reduced_costs(d_list_, d_out_list_, d_count_, list_bound_, mult,
                                           leaving_col, leaving_value, entering_col, d_rc_,
                                           S(stream_)),
         "rc update");

@@ -65,6 +65,32 @@ struct RowWiseArgs {
   int algorithm;  // 0 single row, 1 hypersparse, 2 row-wise
 };
 
+// The hypersparse update row of a large LP straight to its list, one
+// workgroup (row_wise_list_kernel): algorithm 0 or 1, at most kListRowsMax
+// filtered rows holding at most kListEntriesMax entries together (checked by
+// the host). No flags and no N-sized pass: the entries are merged by column
+// in LDS (12 B per entry + 2 B of permutation: 56 KB at the cap).
+constexpr int kListEntriesMax = 4096;
+constexpr int kListRowsMax = 64;
+struct RowWiseListArgs {
+  const int64_t* t_starts;  // CSR of [A | I]
+  const int32_t* t_cols;
+  const double* t_vals;
+  const int32_t* filtered_rows;  // ascending
+  const double* rho;             // rho value per filtered row
+  int num_filtered;
+  const uint64_t* relevant;
+  double* coefficient;  // scattered: touched (algorithm 1) / listed (0) columns
+  double drop_tolerance;
+  int algorithm;  // 0 single row, 1 hypersparse
+  int32_t* list;  // ascending listed columns
+  double* vals;
+  int* count;
+  int32_t* host_list;  // optional mapped host mirrors
+  double* host_vals;
+  int* host_count;
+};
+
 // The whole row-wise update row of a small LP in ONE workgroup and one launch
 // (row_wise_small_kernel): N <= kSmallLdsCols, 1 <= filtered rows <=
 // kSmallRowsMax, their entries <= kSmallEntries (checked by the host). The
@@ -218,7 +244,7 @@ struct DualRatioArgs {
   const int32_t* list;       // update-row positions (list order)
   const double* list_coeff;  // their coefficients
   const int* count;          // list length (device)
-  int max_count;             // N (grid bound)
+  int max_count;             // host-known bound of *count (sizes the grids)
   const double* rc;
   const uint8_t* colbits;
   const double* bound_diff;  // upper - lower per column
@@ -439,6 +465,12 @@ inline int scan_tiles(int n) {
   return n <= 0 ? 1 : (n + milp_kernels::kScanTile - 1) / milp_kernels::kScanTile;
 }
 hipError_t row_wise_update(const milp_kernels::RowWiseArgs& args, hipStream_t s);
+// entries: the filtered rows' total length (<= kListEntriesMax).
+hipError_t row_wise_list(const milp_kernels::RowWiseListArgs& args, int entries, hipStream_t s);
+// flags[list[i]] = 1 for i < *count (flags cleared by the caller; max_count
+// sizes the grid).
+hipError_t flags_from_list(const int32_t* list, const int* count, int max_count, uint8_t* flags,
+                           hipStream_t s);
 // threads: 1024, or 256 (used when the filtered rows fit one per thread).
 hipError_t row_wise_update_small(const milp_kernels::RowWiseSmallArgs& args, int threads,
                                  hipStream_t s);
@@ -462,6 +494,12 @@ hipError_t dual_ratio_bound(const milp_kernels::DualRatioArgs& args, hipStream_t
 hipError_t dual_ratio_select(const milp_kernels::DualRatioArgs& args,
                              const milp_kernels::DualSelectOut& out,
                              const milp_kernels::ScanState& st, hipStream_t s);
+// Both passes in one launch of one workgroup, for lists of at most
+// kDualOneWgMax slots (args.max_count): the block minimum B goes to
+// *args.best (where the tightening round reads it), the selection as above.
+constexpr int kDualOneWgMax = 8192;
+hipError_t dual_ratio_one_wg(const milp_kernels::DualRatioArgs& args,
+                             const milp_kernels::DualSelectOut& out, hipStream_t s);
 // Tighter bound: sort keys (ratio, order-preserving bits) of the pass-2 slots.
 hipError_t dual_ratio_keys(const milp_kernels::DualRatioArgs& args, const int32_t* slots,
                            int num_slots, unsigned long long* keys, hipStream_t s);

@@ -416,7 +416,8 @@ __device__ int scan_look_back(const ScanState& st, int tile, int count) {
   return prefix;
 }
 
-// Block-wide exclusive scan of one int per thread (kScanThreads threads).
+// Block-wide exclusive scan of one int per thread (THREADS threads).
+template <int THREADS = kScanThreads>
 __device__ __forceinline__ int scan_block_exclusive(int c, int* total, int* lds_waves) {
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
@@ -430,7 +431,7 @@ __device__ __forceinline__ int scan_block_exclusive(int c, int* total, int* lds_
   __syncthreads();
   int before = 0, all = 0;
 #pragma unroll
-  for (int w = 0; w < kScanThreads / kWave; ++w) {
+  for (int w = 0; w < THREADS / kWave; ++w) {
     const int v = lds_waves[w];
     before += w < wave ? v : 0;
     all += v;
@@ -565,6 +566,169 @@ __global__ __launch_bounds__(256) void row_wise_update_kernel(RowWiseArgs a) {
       a.coefficient[pos] = touched[l] ? v : 0.0;
     }
     a.flags[pos] = listed ? 1 : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Hypersparse update row of a large LP straight to its list, one workgroup
+// (RowWiseListArgs): the filtered rows hold a few thousand entries out of N
+// columns, so nothing here is sized by N. All entries go to LDS as (column,
+// multiplier * value); every entry then finds its place in the merged column
+// order by ranking: its index in its own row plus, for every other filtered
+// row, the number of that row's columns before it (columns ascend within a
+// row: a binary search; equal columns keep filtered-row order). The head of
+// each run of equal columns folds the run in that order -- the first product
+// is assigned, later ones are added, as row_wise_update_kernel does -- and a
+// block scan compacts the listed heads. Same write rules as that kernel's
+// epilogue, without the flags.
+constexpr int kListThreads = 1024;
+constexpr int kListItems = kListEntriesMax / kListThreads;
+static_assert(kListItems * kListThreads == kListEntriesMax, "whole slots per thread");
+static_assert(kListRowsMax <= kWave, "one wave scans the row lengths");
+static_assert(kListEntriesMax <= 65536, "16-bit permutation");
+
+__global__ __launch_bounds__(kListThreads) void row_wise_list_kernel(RowWiseListArgs a) {
+  __shared__ int32_t s_col[kListEntriesMax];
+  __shared__ double s_prod[kListEntriesMax];
+  __shared__ uint16_t s_perm[kListEntriesMax];  // merged place -> entry
+  __shared__ int s_off[kListRowsMax + 1];       // first entry of each filtered row
+  __shared__ int64_t s_start[kListRowsMax];
+  __shared__ int s_maxlen;
+  __shared__ int lds_waves[kListThreads / kWave];
+  const int t = threadIdx.x;
+  const int k = min(a.num_filtered, kListRowsMax);
+  if (t < kWave) {
+    int len = 0;
+    if (t < k) {
+      const int r = a.filtered_rows[t];
+      const int64_t s = a.t_starts[r];
+      len = static_cast<int>(a.t_starts[r + 1] - s);
+      s_start[t] = s;
+    }
+    int x = len, mx = len;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      const int y = __shfl_up(x, off, kWave);
+      const int z = __shfl_up(mx, off, kWave);
+      if (t >= off) {
+        x += y;
+        mx = max(mx, z);
+      }
+    }
+    if (t < k) s_off[t] = x - len;
+    if (t == kWave - 1) {
+      s_off[k] = x;
+      s_maxlen = mx;
+    }
+  }
+  __syncthreads();
+  const int total_entries = min(s_off[k], kListEntriesMax);
+  // The entries, row by row: entry e of the whole set is thread e % threads'.
+  int my_row[kListItems];
+#pragma unroll
+  for (int it = 0; it < kListItems; ++it) {
+    const int e = t + it * kListThreads;
+    my_row[it] = 0;
+    if (e < total_entries) {
+      int lo = 0, hi = k - 1;  // the row j with s_off[j] <= e < s_off[j + 1]
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (s_off[mid + 1] <= e) lo = mid + 1; else hi = mid;
+      }
+      const int64_t i = s_start[lo] + (e - s_off[lo]);
+      s_col[e] = a.t_cols[i];
+      s_prod[e] = a.rho[lo] * a.t_vals[i];
+      my_row[it] = lo;
+    }
+  }
+  __syncthreads();
+  // Ranking. Rows before the entry's own count their columns <= its column,
+  // rows after it their columns < it: both are "columns < key". The search
+  // takes the same number of steps for every row (four rows in flight).
+  int top = 1;
+  while (top * 2 <= s_maxlen) top *= 2;
+#pragma unroll
+  for (int it = 0; it < kListItems; ++it) {
+    const int e = t + it * kListThreads;
+    if (e >= total_entries) continue;
+    const int j = my_row[it];
+    const int c = s_col[e];
+    int rank = e - s_off[j];
+    for (int r0 = 0; r0 < k; r0 += 4) {
+      int b[4], len[4], key[4], pos[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = r0 + u;
+        const bool valid = r < k && r != j;
+        const int rr = valid ? r : 0;
+        b[u] = s_off[rr];
+        len[u] = valid ? s_off[rr + 1] - b[u] : 0;
+        key[u] = c + (r < j ? 1 : 0);
+        pos[u] = 0;
+      }
+      for (int step = top; step > 0; step >>= 1) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int np = pos[u] + step;
+          const int idx = min(b[u] + np - 1, kListEntriesMax - 1);
+          if (np <= len[u] && s_col[idx] < key[u]) pos[u] = np;
+        }
+      }
+      rank += pos[0] + pos[1] + pos[2] + pos[3];
+    }
+    if (rank < total_entries) s_perm[rank] = static_cast<uint16_t>(e);
+  }
+  __syncthreads();
+  // Merged place m: thread t owns places [t * per, (t + 1) * per).
+  const int per = (total_entries + kListThreads - 1) / kListThreads;
+  unsigned keep = 0;
+  int head_col[kListItems];
+  double head_val[kListItems];
+#pragma unroll
+  for (int i = 0; i < kListItems; ++i) {
+    const int m = t * per + i;
+    head_col[i] = 0;
+    head_val[i] = 0.0;
+    if (i >= per || m >= total_entries) continue;
+    const int e = s_perm[m];
+    const int c = s_col[e];
+    if (m > 0 && s_col[s_perm[m - 1]] == c) continue;  // not the head of its run
+    double v = s_prod[e];
+    for (int m2 = m + 1; m2 < total_entries; ++m2) {
+      const int e2 = s_perm[m2];
+      if (s_col[e2] != c) break;
+      v = a.algorithm == 0 ? s_prod[e2] : v + s_prod[e2];  // single row: one per position
+    }
+    const bool listed = bit_set(a.relevant, c) && fabs(v) > a.drop_tolerance;
+    if (listed || a.algorithm != 0) a.coefficient[c] = v;
+    if (listed) keep |= 1u << i;
+    head_col[i] = c;
+    head_val[i] = v;
+  }
+  int total;
+  int pos = scan_block_exclusive<kListThreads>(__popc(keep), &total, lds_waves);
+#pragma unroll
+  for (int i = 0; i < kListItems; ++i) {
+    if (!(keep & (1u << i))) continue;
+    a.list[pos] = head_col[i];
+    a.vals[pos] = head_val[i];
+    if (a.host_list != nullptr) {  // zero-copy readback into mapped host memory
+      a.host_list[pos] = head_col[i];
+      a.host_vals[pos] = head_val[i];
+    }
+    ++pos;
+  }
+  if (t == 0) {
+    *a.count = total;
+    if (a.host_count != nullptr) *a.host_count = total;
+  }
+}
+
+// The flags the list kernel does not write, for the passes that read them.
+__global__ void flags_from_list_kernel(const int32_t* list, const int* count, uint8_t* flags) {
+  const int n = *count;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    flags[list[i]] = 1;
   }
 }
 
@@ -1327,7 +1491,9 @@ __global__ __launch_bounds__(kScanThreads) void dual_ratio_select_kernel(DualRat
   __shared__ int lds_waves[kScanThreads / kWave];
   const int n = *a.count;
   const int tile = scan_take_tile(st, &lds_tile);
-  const int last_tile = n > 0 ? (n - 1) / kScanTile : 0;
+  // A grid too short for the list (never expected: the host bounds the list
+  // length from above) still reports the true length, and the host fails.
+  const int last_tile = min(n > 0 ? (n - 1) / kScanTile : 0, static_cast<int>(gridDim.x) - 1);
   if (tile <= last_tile) {
     const unsigned long long best = *a.bound;
     const double bound = best == ~0ull ? HUGE_VAL
@@ -1369,6 +1535,84 @@ __global__ __launch_bounds__(kScanThreads) void dual_ratio_select_kernel(DualRat
     }
   }
   scan_finish(st);
+}
+
+// Both passes for a short list in one workgroup: thread t owns the slots
+// [t * per, (t + 1) * per), evaluates each breakpoint once (same
+// expressions), the block minimum of pass 1 is B, and pass 2 filters the
+// ratios kept in registers and compacts them in list order. No tickets, no
+// status words; B is stored where the tightening round reads it.
+constexpr int kOneWgThreads = 1024;
+constexpr int kOneWgItems = milp_launch::kDualOneWgMax / kOneWgThreads;
+static_assert(kOneWgItems * kOneWgThreads == milp_launch::kDualOneWgMax, "whole slots per thread");
+
+__global__ __launch_bounds__(kOneWgThreads) void dual_ratio_one_wg_kernel(DualRatioArgs a,
+                                                                          DualSelectOut out) {
+  __shared__ unsigned long long wave_min[kOneWgThreads / kWave];
+  __shared__ int lds_waves[kOneWgThreads / kWave];
+  const int t = threadIdx.x;
+  const int n_list = *a.count;
+  // A list longer than the cap is never expected (the host bounds it): the
+  // true length is reported and the host fails.
+  const int n = max(0, min(n_list, milp_launch::kDualOneWgMax));
+  const int per = (n + kOneWgThreads - 1) / kOneWgThreads;
+  double ratios[kOneWgItems];
+  unsigned eligible = 0;
+  unsigned long long best = ~0ull;
+#pragma unroll
+  for (int i = 0; i < kOneWgItems; ++i) {
+    const int slot = t * per + i;
+    ratios[i] = 0.0;
+    if (i >= per || slot >= n) continue;
+    double ratio, harris;
+    bool sets_bound;
+    if (!dual_breakpoint(a, slot, &ratio, &harris, &sets_bound)) continue;
+    eligible |= 1u << i;
+    ratios[i] = ratio;
+    if (sets_bound) {
+      const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(harris));
+      best = b < best ? b : best;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_down(best, off, kWave);
+    best = o < best ? o : best;
+  }
+  if ((t & (kWave - 1)) == 0) wave_min[t / kWave] = best;
+  __syncthreads();
+  best = wave_min[0];
+#pragma unroll
+  for (int w = 1; w < kOneWgThreads / kWave; ++w) best = wave_min[w] < best ? wave_min[w] : best;
+  const double bound = best == ~0ull ? HUGE_VAL
+                                     : __longlong_as_double(static_cast<long long>(best)) *
+                                           (1.0 + 1e-9);
+  unsigned keep = 0;
+#pragma unroll
+  for (int i = 0; i < kOneWgItems; ++i) {
+    if ((eligible & (1u << i)) && ratios[i] <= bound) keep |= 1u << i;
+  }
+  int total;
+  int pos = scan_block_exclusive<kOneWgThreads>(__popc(keep), &total, lds_waves);
+  while (keep != 0) {
+    const int i = __ffs(keep) - 1;
+    keep &= keep - 1;
+    const int slot = t * per + i;
+    const int col = a.list[slot];
+    out.slots[pos] = slot;
+    if (pos < out.host_cap) {
+      out.cand_col[pos] = col;
+      out.cand_coeff[pos] = a.list_coeff[slot];
+      out.cand_rc[pos] = a.rc[col];
+    }
+    ++pos;
+  }
+  if (t == 0) {
+    *a.best = best;
+    if (a.best_next != nullptr) *a.best_next = ~0ull;
+    *out.num_slots = total;
+    out.counts[0] = total;
+    out.counts[1] = n_list;
+  }
 }
 
 __device__ __forceinline__ unsigned long long order_bits(double x) {
@@ -1915,6 +2159,14 @@ hipError_t row_wise_update(const RowWiseArgs& args, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t row_wise_list(const RowWiseListArgs& args, int entries, hipStream_t s) {
+  if (args.num_filtered > kListRowsMax || entries > kListEntriesMax || args.algorithm > 1) {
+    return hipErrorInvalidValue;
+  }
+  row_wise_list_kernel<<<1, kListThreads, 0, s>>>(args);
+  return hipGetLastError();
+}
+
 hipError_t row_wise_update_small(const RowWiseSmallArgs& args, int threads, hipStream_t s) {
   if (args.num_cols > kSmallLdsCols || args.num_filtered > kSmallRowsMax ||
       args.num_filtered < 0) {
@@ -2015,6 +2267,12 @@ hipError_t row_wise_update_full_rows(const RowWiseFullArgs& args, hipStream_t s)
 
 static inline int grid_for(int n) { return std::max(1, std::min(4096, div_up(n, 256))); }
 
+hipError_t flags_from_list(const int32_t* list, const int* count, int max_count, uint8_t* flags,
+                           hipStream_t s) {
+  flags_from_list_kernel<<<grid_for(max_count), 256, 0, s>>>(list, count, flags);
+  return hipGetLastError();
+}
+
 hipError_t dual_ratio_bound(const DualRatioArgs& args, hipStream_t s) {
   dual_ratio_bound_kernel<<<grid_for(args.max_count), 256, 0, s>>>(args);
   return hipGetLastError();
@@ -2023,6 +2281,13 @@ hipError_t dual_ratio_bound(const DualRatioArgs& args, hipStream_t s) {
 hipError_t dual_ratio_select(const DualRatioArgs& args, const DualSelectOut& out,
                              const ScanState& st, hipStream_t s) {
   dual_ratio_select_kernel<<<scan_tiles(args.max_count), kScanThreads, 0, s>>>(args, out, st);
+  return hipGetLastError();
+}
+
+hipError_t dual_ratio_one_wg(const DualRatioArgs& args, const DualSelectOut& out,
+                             hipStream_t s) {
+  if (args.max_count > kDualOneWgMax) return hipErrorInvalidValue;
+  dual_ratio_one_wg_kernel<<<1, kOneWgThreads, 0, s>>>(args, out);
   return hipGetLastError();
 }
 
