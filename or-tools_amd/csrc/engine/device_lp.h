@@ -19,6 +19,7 @@
 namespace milp_kernels {
 struct TriSolveArgs;
 struct ScanState;
+struct ListOut;
 struct TightenState;
 }
 namespace sdual {
@@ -347,7 +348,14 @@ class DeviceLp : public DeviceSolver {
   std::vector<int> shard_begin_;
   bool own_mask_dirty_[kNumMasks] = {false, false, false};
   mi_lp_kernel_stats agg_stats_{};
-  void Compact(int n);  // flags_ -> list_ (ascending) + coefficients, async
+  // flags_ -> list_ (ascending) + coefficients, async; bound as ListLaunched.
+  void Compact(int n, int bound);
+  // Where this handle's update-row list goes, with or without the mapped
+  // host mirrors.
+  milp_kernels::ListOut ListOutput(bool mirror) const;
+  // A new list is on its way: at most `bound` columns, `mapped` when it also
+  // lands in the mirrors; its count is known after FetchUpdateRow.
+  void ListLaunched(int bound, bool mapped);
   void NextRowTag();
   void UpdateRowRowWiseSmall(const std::vector<int>& filtered_rows,
                              const std::vector<double>& rho, int algorithm, double drop,

@@ -1083,28 +1083,38 @@ void DeviceLp::FlushRelevantMask() {
 // Compaction of the update-row flags into the ascending list of listed
 // positions plus their coefficients. No host synchronization here: the count
 // comes back with the list in FetchUpdateRow (one round trip per update row).
-void DeviceLp::Compact(int n) {
+void DeviceLp::Compact(int n, int bound) {
+  // The result also lands in mapped host memory (the readback is the sync):
+  // always for small N.
+  const bool mirror = list_mirror_ || n <= milp_launch::kSmallCompactMax;
   if (n <= milp_launch::kSmallCompactMax) {
     // One workgroup: flags -> list + coefficients + count in a single launch.
-    // The result also lands in mapped host memory: the readback is the sync.
-    Check(milp_launch::compact_small(d_flags_, n, d_coeff_, d_list_, d_out_list_, d_count_,
-                                     d_map_list_, d_map_vals_, d_map_count_, S(stream_)),
+    Check(milp_launch::compact_small(d_flags_, n, d_coeff_, ListOutput(mirror), S(stream_)),
           "compact small");
-    mapped_result_ = true;
   } else {
-    // Ordered single-pass compaction over the chip, the list also into
-    // mapped host memory.
-    Check(milp_launch::compact_flags(d_flags_, n, d_coeff_, d_list_, d_out_list_, d_count_,
-                                     list_mirror_ ? d_map_list_ : nullptr,
-                                     list_mirror_ ? d_map_vals_ : nullptr,
-                                     list_mirror_ ? d_map_count_ : nullptr, NextScan(),
+    // Ordered single-pass compaction over the chip.
+    Check(milp_launch::compact_flags(d_flags_, n, d_coeff_, ListOutput(mirror), NextScan(),
                                      S(stream_)),
           "compact");
-    mapped_result_ = list_mirror_;
   }
+  ListLaunched(bound, mirror);
+}
+
+milp_kernels::ListOut DeviceLp::ListOutput(bool mirror) const {
+  milp_kernels::ListOut o{d_list_, d_out_list_, d_count_, nullptr, nullptr, nullptr};
+  if (mirror) {
+    o.host_list = d_map_list_;
+    o.host_vals = d_map_vals_;
+    o.host_count = d_map_count_;
+  }
+  return o;
+}
+
+void DeviceLp::ListLaunched(int bound, bool mapped) {
+  mapped_result_ = mapped;
   list_count_ = -1;  // known after FetchUpdateRow
   ++list_epoch_;
-  list_bound_ = n;  // the row-wise callers know better
+  list_bound_ = bound;
 }
 
 void DeviceLp::UpdateRowColumnWise(const std::vector<double>& rho, double drop,
@@ -1148,7 +1158,7 @@ void DeviceLp::UpdateRowColumnWise(const std::vector<double>& rho, double drop,
   EndKernel(MI_K_UPDATE_ROW, 12.0 * (double(relevant_entries) - dense_entries) +
                                  8.0 * dense_entries + 8.0 * m_ + 9.0 * n_total_ +
                                  (w != nullptr ? 8.0 * m_ : 0.0));
-  Compact(n_total_);
+  Compact(n_total_, n_total_);
   fused_ready_ = (w != nullptr);
 }
 
@@ -1179,22 +1189,14 @@ void DeviceLp::UpdateRowColumnWiseSmall(const std::vector<double>& rho, double d
   a.flags = d_flags_;
   a.out2 = d_out_n_;
   a.drop_tolerance = drop;
-  a.list = d_list_;
-  a.vals_out = d_out_list_;
-  a.count = d_count_;
-  a.host_list = d_map_list_;
-  a.host_vals = d_map_vals_;
-  a.host_count = d_map_count_;
+  a.out = ListOutput(true);
   a.host_dots = d_small_dots_;
   BeginKernel(MI_K_UPDATE_ROW);
   LaunchSmall(milp_kernels::kSmallColWise, a);
   EndKernel(MI_K_UPDATE_ROW, 12.0 * double(relevant_entries) + 8.0 * m_ + 9.0 * n_total_ +
                                  (w != nullptr ? 8.0 * m_ : 0.0));
   small_inflight_ = true;
-  mapped_result_ = true;
-  list_count_ = -1;  // known after FetchUpdateRow
-  ++list_epoch_;
-  list_bound_ = n_total_;
+  ListLaunched(n_total_, true);
   fused_ready_ = (w != nullptr);
   small_dots_mapped_ = (w != nullptr);
 }
@@ -1258,34 +1260,15 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
       k <= milp_kernels::kListRowsMax && entries <= rowwise_list_max_entries_) {
     // Hypersparse: one workgroup merges the rows' entries straight into the
     // list. d_flags_ is not written (FlagsFromList, where a pass reads it).
-    milp_kernels::RowWiseListArgs l{};
-    l.t_starts = d_t_starts_;
-    l.t_cols = d_t_cols_;
-    l.t_vals = d_t_vals_;
-    l.filtered_rows = d_rows;
-    l.rho = d_rho;
-    l.num_filtered = k;
-    l.relevant = d_masks_[kRelevant];
-    l.coefficient = d_coeff_;
-    l.drop_tolerance = drop;
-    l.algorithm = algorithm;
-    l.list = d_list_;
-    l.vals = d_out_list_;
-    l.count = d_count_;
     // The mapped mirrors as Compact writes them: always for small N.
     const bool mirror = list_mirror_ || n_total_ <= milp_launch::kSmallCompactMax;
-    l.host_list = mirror ? d_map_list_ : nullptr;
-    l.host_vals = mirror ? d_map_vals_ : nullptr;
-    l.host_count = mirror ? d_map_count_ : nullptr;
+    const milp_kernels::RowWiseListArgs l{a, ListOutput(mirror)};
     BeginKernel(id);
     Check(milp_launch::row_wise_list(l, static_cast<int>(entries), S(stream_)), "rowwise list");
     // The CSR entries, the rows and multipliers, the list slots (their count
     // is not known here: bounded by the entries).
     EndKernel(id, 12.0 * entries + 12.0 * k + 12.0 * bound);
-    mapped_result_ = mirror;
-    list_count_ = -1;  // known after FetchUpdateRow
-    ++list_epoch_;
-    list_bound_ = bound;
+    ListLaunched(bound, mirror);
     flags_stale_ = true;
     return;
   }
@@ -1314,8 +1297,7 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
     Check(milp_launch::row_wise_update_full_rows(f, S(stream_)), "rowwise full rows");
     // Values only (the column index of entry j is j), the list, the outputs.
     EndKernel(id, 8.0 * double(k) * (num_structural_ + 1) + 12.0 * k + 9.0 * n_total_);
-    Compact(n_total_);
-    list_bound_ = bound;
+    Compact(n_total_, bound);
     return;
   }
   if (k <= rowwise_chunk_max_rows_ || max_col_len_ > kColumnKernelMaxColumnLength) {
@@ -1344,8 +1326,7 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
     Check(milp_launch::row_wise_update_by_column(c, S(stream_)), "rowwise by column");
   }
   EndKernel(id, 12.0 * entries + 12.0 * k + 9.0 * n_total_);
-  Compact(n_total_);
-  list_bound_ = bound;
+  Compact(n_total_, bound);
 }
 
 // Small LPs: inputs in mapped host memory, one launch, the list comes back in
@@ -1378,21 +1359,13 @@ void DeviceLp::UpdateRowRowWiseSmall(const std::vector<int>& filtered_rows,
     c.flags = d_flags_;
     c.drop_tolerance = drop;
     c.algorithm = algorithm;
-    c.list = d_list_;
-    c.list_vals = d_out_list_;
-    c.count = d_count_;
-    c.host_list = d_map_list_;
-    c.host_vals = d_map_vals_;
-    c.host_count = d_map_count_;
+    c.out = ListOutput(true);
     BeginKernel(id);
     LaunchSmall(milp_kernels::kSmallRowWiseByColumn, c);
     // The whole CSC copy, the filtered rows and multipliers, flags/coefficients.
     EndKernel(id, 12.0 * double(nnz_) + 8.0 * (n_total_ + 1) + 12.0 * k + 9.0 * n_total_);
     small_inflight_ = true;
-    mapped_result_ = true;
-    list_count_ = -1;
-    ++list_epoch_;
-    list_bound_ = n_total_;
+    ListLaunched(n_total_, true);
     return;
   }
   milp_kernels::RowWiseSmallArgs a{};
@@ -1408,21 +1381,13 @@ void DeviceLp::UpdateRowRowWiseSmall(const std::vector<int>& filtered_rows,
   a.flags = d_flags_;
   a.drop_tolerance = drop;
   a.algorithm = algorithm;
-  a.list = d_list_;
-  a.vals = d_out_list_;
-  a.count = d_count_;
-  a.host_list = d_map_list_;
-  a.host_vals = d_map_vals_;
-  a.host_count = d_map_count_;
+  a.out = ListOutput(true);
   BeginKernel(id);
   LaunchSmall(medium_ ? milp_kernels::kMediumRowWise : milp_kernels::kSmallRowWise, a);
   // Rows and multipliers, the CSR entries, N-sized flags/coefficients, the list.
   EndKernel(id, 12.0 * entries + 12.0 * k + 9.0 * n_total_);
   small_inflight_ = true;
-  mapped_result_ = true;
-  list_count_ = -1;  // known after FetchUpdateRow
-  ++list_epoch_;
-  list_bound_ = n_total_;
+  ListLaunched(n_total_, true);
 }
 
 void DeviceLp::NextRowTag() {

@@ -50,11 +50,23 @@ struct DenseArgs {
   double* out2;
 };
 
+// Where an update-row kernel that emits the list itself puts it: the
+// ascending listed columns, their coefficients and the count, on the device
+// and (optional, null when off) mirrored into mapped host memory.
+struct ListOut {
+  int32_t* list;
+  double* vals;
+  int* count;
+  int32_t* host_list;
+  double* host_vals;
+  int* host_count;
+};
+
 struct RowWiseArgs {
   const int64_t* t_starts;  // CSR of [A | I] (transposed_matrix_)
   const int32_t* t_cols;
   const double* t_vals;
-  const int32_t* filtered_rows;  // ascending
+  const int32_t* filtered_rows;  // list order (ascending for the chunk and list kernels)
   const double* rho;             // rho value per filtered row
   int num_filtered;
   int num_cols;
@@ -68,27 +80,14 @@ struct RowWiseArgs {
 // The hypersparse update row of a large LP straight to its list, one
 // workgroup (row_wise_list_kernel): algorithm 0 or 1, at most kListRowsMax
 // filtered rows holding at most kListEntriesMax entries together (checked by
-// the host). No flags and no N-sized pass: the entries are merged by column
-// in LDS (12 B per entry + 2 B of permutation: 56 KB at the cap).
+// the host). No flags and no N-sized pass (flags and num_cols are ignored;
+// coefficient is scattered: touched (algorithm 1) / listed (0) columns): the
+// entries are merged by column in LDS (12 B per entry + 2 B of permutation:
+// 56 KB at the cap).
 constexpr int kListEntriesMax = 4096;
 constexpr int kListRowsMax = 64;
-struct RowWiseListArgs {
-  const int64_t* t_starts;  // CSR of [A | I]
-  const int32_t* t_cols;
-  const double* t_vals;
-  const int32_t* filtered_rows;  // ascending
-  const double* rho;             // rho value per filtered row
-  int num_filtered;
-  const uint64_t* relevant;
-  double* coefficient;  // scattered: touched (algorithm 1) / listed (0) columns
-  double drop_tolerance;
-  int algorithm;  // 0 single row, 1 hypersparse
-  int32_t* list;  // ascending listed columns
-  double* vals;
-  int* count;
-  int32_t* host_list;  // optional mapped host mirrors
-  double* host_vals;
-  int* host_count;
+struct RowWiseListArgs : RowWiseArgs {
+  ListOut out;
 };
 
 // The whole row-wise update row of a small LP in ONE workgroup and one launch
@@ -117,12 +116,7 @@ struct ColWiseSmallArgs {
   uint8_t* flags;
   double* out2;            // w . a_j of kept columns (device, per column)
   double drop_tolerance;
-  int32_t* list;  // device copies of the compacted list
-  double* vals_out;
-  int* count;
-  int32_t* host_list;  // mapped host memory
-  double* host_vals;
-  int* host_count;
+  ListOut out;
   double* host_dots;   // mapped host memory, list order (with w)
 };
 
@@ -144,12 +138,7 @@ struct RowWiseSmallColArgs {
   uint8_t* flags;
   double drop_tolerance;
   int algorithm;
-  int32_t* list;
-  double* list_vals;
-  int* count;
-  int32_t* host_list;
-  double* host_vals;
-  int* host_count;
+  ListOut out;
 };
 
 // out[k] = a_{list[k]} . y for a small LP without a dense block, one
@@ -168,26 +157,9 @@ struct ListDotsSmallArgs {
 };
 constexpr int kSmallRowsMax = 1024;
 constexpr int kSmallEntries = 4096;
-struct RowWiseSmallArgs {
-  const int64_t* t_starts;
-  const int32_t* t_cols;
-  const double* t_vals;
-  const int32_t* filtered_rows;  // mapped host memory, list order
-  const double* rho;             // mapped host memory, rho per filtered row
-  int num_filtered;
-  int num_cols;
-  const uint64_t* relevant;      // mapped host memory
-  double* coefficient;
-  uint8_t* flags;
-  double drop_tolerance;
-  int algorithm;  // 0 single row, 1 hypersparse, 2 row-wise
-  int32_t* list;  // device copies of the compacted list
-  double* vals;
-  int* count;
-  int32_t* host_list;  // mapped host memory
-  double* host_vals;
-  int* host_count;
-};
+// RowWiseArgs with filtered_rows (list order), rho and relevant in mapped
+// host memory, plus the list output.
+using RowWiseSmallArgs = RowWiseListArgs;
 constexpr int kMediumCols = 65536;
 
 // The row-wise update row when every filtered row is full (all structural
@@ -332,6 +304,7 @@ struct SmallSlot {
     RowWiseSmallColArgs rc;
   };
 };
+static_assert(sizeof(SmallSlot) % 4 == 0, "the batch kernel stages a slot as 32-bit words");
 constexpr int kSmallBatchMax = 128;  // requests per launch
 struct SmallBatchArgs {
   const SmallSlot* slots;       // device view of the mapped slot table
@@ -451,15 +424,13 @@ hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hi
 // Flags -> ascending list + coefficient gather + count, one workgroup, for
 // n <= kSmallCompactMax.
 constexpr int kSmallCompactMax = 1 << 14;  // one workgroup writes the list to host memory
-// host_* (optional, device-visible mapped host memory) receive a copy.
-hipError_t compact_small(const uint8_t* flags, int n, const double* coeff, int32_t* list,
-                         double* vals, int* count, int32_t* host_list, double* host_vals,
-                         int* host_count, hipStream_t s);
+hipError_t compact_small(const uint8_t* flags, int n, const double* coeff,
+                         const milp_kernels::ListOut& out, hipStream_t s);
 // Any n: flags -> ascending list + coefficients + count in one launch
-// (ordered single-pass compaction); host_* as above.
-hipError_t compact_flags(const uint8_t* flags, int n, const double* coeff, int32_t* list,
-                         double* vals, int* count, int32_t* host_list, double* host_vals,
-                         int* host_count, const milp_kernels::ScanState& st, hipStream_t s);
+// (ordered single-pass compaction).
+hipError_t compact_flags(const uint8_t* flags, int n, const double* coeff,
+                         const milp_kernels::ListOut& out, const milp_kernels::ScanState& st,
+                         hipStream_t s);
 // Tiles a compaction launch over n slots uses (ScanState::status length).
 inline int scan_tiles(int n) {
   return n <= 0 ? 1 : (n + milp_kernels::kScanTile - 1) / milp_kernels::kScanTile;

@@ -325,46 +325,73 @@ __global__ void gather_kernel(const int32_t* list, int n, const double* src, dou
     dst[i] = src[list[i]];
 }
 
+// ---------------------------------------------------------------------------
+// The pieces every update-row kernel that emits its list shares: the block
+// scan that places the listed columns, and the two stores into a ListOut.
+
+// Block-wide exclusive scan of one int per thread (THREADS threads, all of
+// them call it); *total = the sum over the block. lds_waves holds THREADS /
+// kWave ints. The only barrier sits between writing and reading lds_waves:
+// a caller that scans twice through the same lds_waves owns a barrier between
+// the two calls (a slow wave may still be reading the first call's sums).
+template <int THREADS = kScanThreads>
+__device__ __forceinline__ int scan_block_exclusive(int c, int* total, int* lds_waves) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  int x = c;
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const int y = __shfl_up(x, off, kWave);
+    if (lane >= off) x += y;
+  }
+  if (lane == kWave - 1) lds_waves[wave] = x;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < THREADS / kWave; ++w) {
+    const int v = lds_waves[w];
+    before += w < wave ? v : 0;
+    all += v;
+  }
+  *total = all;
+  return before + x - c;
+}
+
+// List slot `pos` = (col, v); the mapped host mirror is the zero-copy readback.
+__device__ __forceinline__ void list_store(const ListOut& o, int pos, int32_t col, double v) {
+  o.list[pos] = col;
+  o.vals[pos] = v;
+  if (o.host_list != nullptr) {
+    o.host_list[pos] = col;
+    o.host_vals[pos] = v;
+  }
+}
+
+__device__ __forceinline__ void list_store_count(const ListOut& o, int n) {
+  *o.count = n;
+  if (o.host_count != nullptr) *o.host_count = n;
+}
+
 // Update-row compaction for small N in one workgroup: thread t owns a
 // contiguous slice of the flags, a block-wide exclusive scan of the slice
 // counts gives each thread its output offset, so the list comes out in
 // ascending position order, as rocprim::select would produce it.
 constexpr int kCompactThreads = 1024;
 __global__ __launch_bounds__(kCompactThreads) void compact_small_kernel(
-    const uint8_t* flags, int n, const double* coeff, int32_t* list, double* vals, int* count,
-    int32_t* host_list, double* host_vals, int* host_count) {
-  __shared__ int sums[kCompactThreads];
+    const uint8_t* flags, int n, const double* coeff, ListOut out) {
+  __shared__ int lds_waves[kCompactThreads / kWave];
   const int t = threadIdx.x;
   const int per = (n + kCompactThreads - 1) / kCompactThreads;
   const int b = min(n, t * per);
   const int e = min(n, b + per);
   int c = 0;
   for (int i = b; i < e; ++i) c += flags[i] != 0;
-  sums[t] = c;
-  __syncthreads();
-  for (int off = 1; off < kCompactThreads; off <<= 1) {
-    const int v = t >= off ? sums[t - off] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  int pos = sums[t] - c;
+  int total;
+  int pos = scan_block_exclusive<kCompactThreads>(c, &total, lds_waves);
   for (int i = b; i < e; ++i) {
-    if (flags[i] != 0) {
-      const double v = coeff[i];
-      list[pos] = i;
-      vals[pos] = v;
-      if (host_list != nullptr) {  // zero-copy readback into mapped host memory
-        host_list[pos] = i;
-        host_vals[pos] = v;
-      }
-      ++pos;
-    }
+    if (flags[i] != 0) list_store(out, pos++, i, coeff[i]);
   }
-  if (t == kCompactThreads - 1) {
-    *count = sums[t];
-    if (host_count != nullptr) *host_count = sums[t];
-  }
+  if (t == 0) list_store_count(out, total);
 }
 
 // ---------------------------------------------------------------------------
@@ -416,30 +443,6 @@ __device__ int scan_look_back(const ScanState& st, int tile, int count) {
   return prefix;
 }
 
-// Block-wide exclusive scan of one int per thread (THREADS threads).
-template <int THREADS = kScanThreads>
-__device__ __forceinline__ int scan_block_exclusive(int c, int* total, int* lds_waves) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  int x = c;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int y = __shfl_up(x, off, kWave);
-    if (lane >= off) x += y;
-  }
-  if (lane == kWave - 1) lds_waves[wave] = x;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < THREADS / kWave; ++w) {
-    const int v = lds_waves[w];
-    before += w < wave ? v : 0;
-    all += v;
-  }
-  *total = all;
-  return before + x - c;
-}
-
 __device__ __forceinline__ int scan_take_tile(const ScanState& st, int* lds_tile) {
   if (threadIdx.x == 0) *lds_tile = static_cast<int>(atomicAdd(st.ticket, 1u));
   __syncthreads();
@@ -458,8 +461,7 @@ __device__ __forceinline__ void scan_finish(const ScanState& st) {
 }
 
 __global__ __launch_bounds__(kScanThreads) void compact_flags_kernel(
-    const uint8_t* flags, int n, const double* coeff, int32_t* list, double* vals, int* count,
-    int32_t* host_list, double* host_vals, int* host_count, ScanState st) {
+    const uint8_t* flags, int n, const double* coeff, ListOut out, ScanState st) {
   __shared__ int lds_tile, lds_prefix;
   __shared__ int lds_waves[kScanThreads / kWave];
   const int tile = scan_take_tile(st, &lds_tile);
@@ -486,19 +488,10 @@ __global__ __launch_bounds__(kScanThreads) void compact_flags_kernel(
     const int i = __ffs(keep) - 1;
     keep &= keep - 1;
     const int slot = base + i;
-    const double v = coeff[slot];
-    list[pos] = slot;
-    vals[pos] = v;
-    if (host_list != nullptr) {  // zero-copy readback into mapped host memory
-      host_list[pos] = slot;
-      host_vals[pos] = v;
-    }
-    ++pos;
+    list_store(out, pos++, slot, coeff[slot]);
   }
   if (tile == static_cast<int>(gridDim.x) - 1 && threadIdx.x == 0) {
-    const int all = lds_prefix + total;
-    *count = all;
-    if (host_count != nullptr) *host_count = all;
+    list_store_count(out, lds_prefix + total);
   }
   scan_finish(st);
 }
@@ -512,6 +505,33 @@ __global__ __launch_bounds__(kScanThreads) void compact_flags_kernel(
 // row order, as in the host scatter loops. Accumulators live in LDS.
 constexpr int kChunk = 256;
 
+// The write rule of the row-wise update row per algorithm (update_row.cc:
+// 196-280), in two steps every row-wise kernel goes through. Accumulation:
+// `first` = nothing was written to the position yet; the single-row
+// algorithm 0 assigns every product, so its callers pass first = true.
+__device__ __forceinline__ double row_wise_accumulate(double acc, bool first, double v,
+                                                      int algorithm) {
+  if (!first) return acc + v;
+  return algorithm == 2 ? 0.0 + v : v;  // AssignToZero then +=, or first assign
+}
+
+// Epilogue: what goes to coefficient[col]; returns whether col is listed.
+__device__ __forceinline__ bool row_wise_store(int algorithm, bool touched, bool rel, double acc,
+                                               double drop_tolerance, double* coefficient,
+                                               int col) {
+  bool listed;
+  if (algorithm == 0) {
+    listed = touched && rel && fabs(acc) > drop_tolerance;
+    if (listed) coefficient[col] = acc;
+  } else if (algorithm == 1) {
+    listed = touched && rel && fabs(acc) > drop_tolerance;
+    if (touched) coefficient[col] = acc;
+  } else {
+    listed = rel && fabs(acc) > drop_tolerance;
+    coefficient[col] = touched ? acc : 0.0;
+  }
+  return listed;
+}
 
 __global__ __launch_bounds__(256) void row_wise_update_kernel(RowWiseArgs a) {
   __shared__ double acc[kChunk];
@@ -539,32 +559,15 @@ __global__ __launch_bounds__(256) void row_wise_update_kernel(RowWiseArgs a) {
       if (pos >= c1) break;
       const double v = multiplier * a.t_vals[i];
       const int l = pos - c0;
-      if (a.algorithm == 0) {
-        acc[l] = v;  // single row: one contribution per position
-      } else if (a.algorithm == 1) {
-        acc[l] = touched[l] ? acc[l] + v : v;  // hypersparse: first is assigned
-      } else {
-        acc[l] = touched[l] ? acc[l] + v : 0.0 + v;  // row-wise: 0.0 += v
-      }
+      acc[l] = row_wise_accumulate(acc[l], a.algorithm == 0 || !touched[l], v, a.algorithm);
       touched[l] = 1;
     }
     __syncthreads();  // rows are applied in order
   }
   for (int l = threadIdx.x; l < c1 - c0; l += blockDim.x) {
     const int pos = c0 + l;
-    const double v = acc[l];
-    const bool rel = bit_set(a.relevant, pos);
-    bool listed;
-    if (a.algorithm == 0) {
-      listed = touched[l] && rel && fabs(v) > a.drop_tolerance;
-      if (listed) a.coefficient[pos] = v;
-    } else if (a.algorithm == 1) {
-      listed = touched[l] && rel && fabs(v) > a.drop_tolerance;
-      if (touched[l]) a.coefficient[pos] = v;
-    } else {
-      listed = rel && fabs(v) > a.drop_tolerance;
-      a.coefficient[pos] = touched[l] ? v : 0.0;
-    }
+    const bool listed = row_wise_store(a.algorithm, touched[l], bit_set(a.relevant, pos), acc[l],
+                                       a.drop_tolerance, a.coefficient, pos);
     a.flags[pos] = listed ? 1 : 0;
   }
 }
@@ -693,14 +696,14 @@ __global__ __launch_bounds__(kListThreads) void row_wise_list_kernel(RowWiseList
     const int e = s_perm[m];
     const int c = s_col[e];
     if (m > 0 && s_col[s_perm[m - 1]] == c) continue;  // not the head of its run
-    double v = s_prod[e];
+    double v = s_prod[e];  // the run's first product is assigned (algorithms 0 and 1)
     for (int m2 = m + 1; m2 < total_entries; ++m2) {
       const int e2 = s_perm[m2];
       if (s_col[e2] != c) break;
-      v = a.algorithm == 0 ? s_prod[e2] : v + s_prod[e2];  // single row: one per position
+      v = row_wise_accumulate(v, a.algorithm == 0, s_prod[e2], a.algorithm);
     }
-    const bool listed = bit_set(a.relevant, c) && fabs(v) > a.drop_tolerance;
-    if (listed || a.algorithm != 0) a.coefficient[c] = v;
+    const bool listed = row_wise_store(a.algorithm, true, bit_set(a.relevant, c), v,
+                                       a.drop_tolerance, a.coefficient, c);
     if (listed) keep |= 1u << i;
     head_col[i] = c;
     head_val[i] = v;
@@ -709,19 +712,9 @@ __global__ __launch_bounds__(kListThreads) void row_wise_list_kernel(RowWiseList
   int pos = scan_block_exclusive<kListThreads>(__popc(keep), &total, lds_waves);
 #pragma unroll
   for (int i = 0; i < kListItems; ++i) {
-    if (!(keep & (1u << i))) continue;
-    a.list[pos] = head_col[i];
-    a.vals[pos] = head_val[i];
-    if (a.host_list != nullptr) {  // zero-copy readback into mapped host memory
-      a.host_list[pos] = head_col[i];
-      a.host_vals[pos] = head_val[i];
-    }
-    ++pos;
+    if (keep & (1u << i)) list_store(a.out, pos++, head_col[i], head_val[i]);
   }
-  if (t == 0) {
-    *a.count = total;
-    if (a.host_count != nullptr) *a.host_count = total;
-  }
+  if (t == 0) list_store_count(a.out, total);
 }
 
 // The flags the list kernel does not write, for the passes that read them.
@@ -743,6 +736,49 @@ __global__ void flags_from_list_kernel(const int32_t* list, const int* count, ui
 // memory. Arithmetic as row_wise_update_kernel: the rows are applied in list
 // order with a barrier between rows (a position appears once per row, so one
 // thread owns it within a row), with the same first-write rule per algorithm.
+
+// The staging the small and medium bodies share: the filtered rows' rho
+// values, CSR offsets and, by a block scan of their lengths, the first entry
+// of each row in the concatenation of all their entries.
+struct RowStage {
+  double rho[kSmallRowsMax];
+  int64_t off[kSmallRowsMax];
+  int beg[kSmallRowsMax + 1];
+};
+
+// Wave 1: row extents (one row per thread: num_filtered <= THREADS). Returns
+// the number of entries. The closing barrier publishes the stage and ends the
+// scan's use of lds_waves, so the caller may scan through it again.
+template <int THREADS>
+__device__ __forceinline__ int stage_rows(const RowWiseArgs& a, RowStage& s, int* lds_waves) {
+  const int t = threadIdx.x;
+  int len = 0;
+  if (t < a.num_filtered) {
+    const int r = a.filtered_rows[t];
+    s.rho[t] = a.rho[t];
+    const int64_t b = a.t_starts[r];
+    s.off[t] = b;
+    len = static_cast<int>(a.t_starts[r + 1] - b);
+  }
+  int total;
+  const int beg = scan_block_exclusive<THREADS>(len, &total, lds_waves);
+  if (t < a.num_filtered) s.beg[t] = beg;
+  if (t == 0) s.beg[a.num_filtered] = total;
+  __syncthreads();
+  return total;
+}
+
+// The filtered row holding entry e: the last k with beg[k] <= e.
+__device__ __forceinline__ int stage_row_of(const RowStage& s, int k_rows, int e) {
+  int lo = 0;
+  int hi = k_rows - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (s.beg[mid] <= e) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 template <int THREADS>
 __device__ __forceinline__ void row_wise_small_body(const RowWiseSmallArgs& a) {
   __shared__ double acc[kSmallLdsCols];
@@ -750,62 +786,28 @@ __device__ __forceinline__ void row_wise_small_body(const RowWiseSmallArgs& a) {
   __shared__ uint64_t rel[kSmallLdsCols / 64];
   __shared__ int32_t ent_pos[kSmallEntries];
   __shared__ double ent_val[kSmallEntries];
-  __shared__ double s_rho[kSmallRowsMax];
-  __shared__ int64_t s_off[kSmallRowsMax];
-  __shared__ int s_beg[kSmallRowsMax + 1];
-  __shared__ int sums[THREADS];
+  __shared__ RowStage rows;
+  __shared__ int lds_waves[THREADS / kWave];
   const int t = threadIdx.x;
   const int n = a.num_cols;
   const int k_rows = a.num_filtered;
   for (int i = t; i < n; i += THREADS) touched[i] = 0;
   for (int w = t; w < (n + 63) / 64; w += THREADS) rel[w] = a.relevant[w];
-  // Wave 1: row extents (one row per thread; k_rows <= THREADS).
-  int len = 0;
-  if (t < k_rows) {
-    const int r = a.filtered_rows[t];
-    s_rho[t] = a.rho[t];
-    const int64_t b = a.t_starts[r];
-    s_off[t] = b;
-    len = static_cast<int>(a.t_starts[r + 1] - b);
-  }
-  sums[t] = len;
-  __syncthreads();
-  for (int off = 1; off < THREADS; off <<= 1) {
-    const int v = t >= off ? sums[t - off] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  if (t < k_rows) s_beg[t] = sums[t] - len;
-  if (t == 0) s_beg[k_rows] = sums[THREADS - 1];
-  __syncthreads();
+  // At most kSmallEntries entries (host-checked).
+  const int num_entries = stage_rows<THREADS>(a, rows, lds_waves);
   // Wave 2: every entry of every filtered row, product rho_k * A[r_k, pos].
-  const int num_entries = s_beg[k_rows];  // <= kSmallEntries (host-checked)
   for (int e = t; e < num_entries; e += THREADS) {
-    int lo = 0;
-    int hi = k_rows - 1;
-    while (lo < hi) {  // last row k with s_beg[k] <= e
-      const int mid = (lo + hi + 1) >> 1;
-      if (s_beg[mid] <= e) lo = mid; else hi = mid - 1;
-    }
-    const int64_t i = s_off[lo] + (e - s_beg[lo]);
+    const int k = stage_row_of(rows, k_rows, e);
+    const int64_t i = rows.off[k] + (e - rows.beg[k]);
     ent_pos[e] = a.t_cols[i];
-    ent_val[e] = s_rho[lo] * a.t_vals[i];
+    ent_val[e] = rows.rho[k] * a.t_vals[i];
   }
   __syncthreads();
   for (int k = 0; k < k_rows; ++k) {
-    for (int e = s_beg[k] + t; e < s_beg[k + 1]; e += THREADS) {
+    for (int e = rows.beg[k] + t; e < rows.beg[k + 1]; e += THREADS) {
       const int pos = ent_pos[e];
-      const double v = ent_val[e];
-      double out;
-      if (a.algorithm == 0) {
-        out = v;
-      } else if (!touched[pos]) {
-        out = a.algorithm == 2 ? 0.0 + v : v;
-      } else {
-        out = acc[pos] + v;
-      }
-      acc[pos] = out;
+      acc[pos] = row_wise_accumulate(acc[pos], a.algorithm == 0 || !touched[pos], ent_val[e],
+                                     a.algorithm);
       touched[pos] = 1;
     }
     __syncthreads();  // rows are applied in order
@@ -815,50 +817,22 @@ __device__ __forceinline__ void row_wise_small_body(const RowWiseSmallArgs& a) {
   const int b = min(n, t * per);
   const int e = min(n, b + per);
   uint32_t listed_bits = 0;
-  int c = 0;
   for (int pos = b; pos < e; ++pos) {
     const bool was_touched = touched[pos] != 0;
-    const double v = was_touched ? acc[pos] : 0.0;
     const bool is_rel = (rel[pos >> 6] >> (pos & 63)) & 1ull;
-    bool listed;
-    if (a.algorithm == 0) {
-      listed = was_touched && is_rel && fabs(v) > a.drop_tolerance;
-      if (listed) a.coefficient[pos] = v;
-    } else if (a.algorithm == 1) {
-      listed = was_touched && is_rel && fabs(v) > a.drop_tolerance;
-      if (was_touched) a.coefficient[pos] = v;
-    } else {
-      listed = is_rel && fabs(v) > a.drop_tolerance;
-      a.coefficient[pos] = was_touched ? v : 0.0;
-    }
+    const bool listed = row_wise_store(a.algorithm, was_touched, is_rel,
+                                       was_touched ? acc[pos] : 0.0, a.drop_tolerance,
+                                       a.coefficient, pos);
     a.flags[pos] = listed ? 1 : 0;
     listed_bits |= uint32_t(listed) << (pos - b);
-    c += listed;
   }
-  __syncthreads();
-  sums[t] = c;
-  __syncthreads();
-  for (int off = 1; off < THREADS; off <<= 1) {
-    const int v = t >= off ? sums[t - off] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  int out_pos = sums[t] - c;
+  int total;
+  int out_pos = scan_block_exclusive<THREADS>(__popc(listed_bits), &total, lds_waves);
   for (int pos = b; pos < e; ++pos) {
-    if ((listed_bits >> (pos - b)) & 1u) {
-      const double v = acc[pos];  // a listed position was touched: its value
-      a.list[out_pos] = pos;
-      a.vals[out_pos] = v;
-      a.host_list[out_pos] = pos;
-      a.host_vals[out_pos] = v;
-      ++out_pos;
-    }
+    // A listed position was touched: acc holds its value.
+    if ((listed_bits >> (pos - b)) & 1u) list_store(a.out, out_pos++, pos, acc[pos]);
   }
-  if (t == THREADS - 1) {
-    *a.count = sums[t];
-    *a.host_count = sums[t];
-  }
+  if (t == 0) list_store_count(a.out, total);
 }
 
 template <int THREADS>
@@ -909,10 +883,8 @@ __device__ __forceinline__ void row_wise_medium_body(const RowWiseSmallArgs& a) 
   __shared__ unsigned long long touched_w[kMediumCols / 64];  // positions in the table
   __shared__ int16_t ent_slot[kSmallEntries];
   __shared__ double ent_val[kSmallEntries];
-  __shared__ double s_rho[kSmallRowsMax];
-  __shared__ int64_t s_off[kSmallRowsMax];
-  __shared__ int s_beg[kSmallRowsMax + 1];
-  __shared__ int sums[THREADS];
+  __shared__ RowStage rows;
+  __shared__ int lds_waves[THREADS / kWave];
   const int t = threadIdx.x;
   const int n = a.num_cols;
   const int k_rows = a.num_filtered;
@@ -925,36 +897,13 @@ __device__ __forceinline__ void row_wise_medium_body(const RowWiseSmallArgs& a) 
     listed_w[w] = 0;
     touched_w[w] = 0;
   }
-  int len = 0;
-  if (t < k_rows) {
-    const int r = a.filtered_rows[t];
-    s_rho[t] = a.rho[t];
-    const int64_t b = a.t_starts[r];
-    s_off[t] = b;
-    len = static_cast<int>(a.t_starts[r + 1] - b);
-  }
-  sums[t] = len;
-  __syncthreads();
-  for (int off = 1; off < THREADS; off <<= 1) {
-    const int v = t >= off ? sums[t - off] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  if (t < k_rows) s_beg[t] = sums[t] - len;
-  if (t == 0) s_beg[k_rows] = sums[THREADS - 1];
-  __syncthreads();
-  const int num_entries = s_beg[k_rows];  // <= kSmallEntries (host-checked)
+  // At most kSmallEntries entries (host-checked).
+  const int num_entries = stage_rows<THREADS>(a, rows, lds_waves);
   for (int e = t; e < num_entries; e += THREADS) {
-    int lo = 0;
-    int hi = k_rows - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (s_beg[mid] <= e) lo = mid; else hi = mid - 1;
-    }
-    const int64_t i = s_off[lo] + (e - s_beg[lo]);
+    const int k = stage_row_of(rows, k_rows, e);
+    const int64_t i = rows.off[k] + (e - rows.beg[k]);
     const int pos = a.t_cols[i];
-    ent_val[e] = s_rho[lo] * a.t_vals[i];
+    ent_val[e] = rows.rho[k] * a.t_vals[i];
     int sl = medium_hash(pos);
     for (int probe = 0; probe < kMediumSlots; ++probe) {
       const int old = atomicCAS(&keys[sl], -1, pos);
@@ -966,18 +915,10 @@ __device__ __forceinline__ void row_wise_medium_body(const RowWiseSmallArgs& a) 
   }
   __syncthreads();
   for (int k = 0; k < k_rows; ++k) {
-    for (int e = s_beg[k] + t; e < s_beg[k + 1]; e += THREADS) {
+    for (int e = rows.beg[k] + t; e < rows.beg[k + 1]; e += THREADS) {
       const int sl = ent_slot[e];
-      const double v = ent_val[e];
-      double out;
-      if (a.algorithm == 0) {
-        out = v;
-      } else if (!written[sl]) {
-        out = a.algorithm == 2 ? 0.0 + v : v;
-      } else {
-        out = acc[sl] + v;
-      }
-      acc[sl] = out;
+      acc[sl] = row_wise_accumulate(acc[sl], a.algorithm == 0 || !written[sl], ent_val[e],
+                                    a.algorithm);
       written[sl] = 1;
     }
     __syncthreads();  // rows are applied in order
@@ -988,47 +929,23 @@ __device__ __forceinline__ void row_wise_medium_body(const RowWiseSmallArgs& a) 
     const bool in_table = (touched_w[pos >> 6] >> (pos & 63)) & 1ull;
     const int sl = in_table ? medium_find(keys, pos) : -1;
     const bool was_touched = sl >= 0 && written[sl] != 0;
-    const double v = was_touched ? acc[sl] : 0.0;
     const bool is_rel = (rel[pos >> 6] >> (pos & 63)) & 1ull;
-    bool listed;
-    if (a.algorithm == 0) {
-      listed = was_touched && is_rel && fabs(v) > a.drop_tolerance;
-      if (listed) a.coefficient[pos] = v;
-    } else if (a.algorithm == 1) {
-      listed = was_touched && is_rel && fabs(v) > a.drop_tolerance;
-      if (was_touched) a.coefficient[pos] = v;
-    } else {
-      listed = is_rel && fabs(v) > a.drop_tolerance;
-      a.coefficient[pos] = was_touched ? v : 0.0;
-    }
+    const bool listed = row_wise_store(a.algorithm, was_touched, is_rel,
+                                       was_touched ? acc[sl] : 0.0, a.drop_tolerance,
+                                       a.coefficient, pos);
     a.flags[pos] = listed ? 1 : 0;
     if (listed) atomicOr(&listed_w[pos >> 6], 1ull << (pos & 63));
   }
-  __syncthreads();
+  __syncthreads();  // listed_w is complete (and lds_waves long free again)
   const uint64_t mine = t < (n + 63) / 64 ? listed_w[t] : 0ull;
-  const int c = __popcll(mine);
-  sums[t] = c;
-  __syncthreads();
-  for (int off = 1; off < THREADS; off <<= 1) {
-    const int v = t >= off ? sums[t - off] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  int out_pos = sums[t] - c;
+  int total;
+  int out_pos = scan_block_exclusive<THREADS>(__popcll(mine), &total, lds_waves);
   for (uint64_t bits = mine; bits != 0; bits &= bits - 1) {
     const int pos = t * 64 + __builtin_ctzll(bits);
-    const double v = acc[medium_find(keys, pos)];  // a listed position was touched
-    a.list[out_pos] = pos;
-    a.vals[out_pos] = v;
-    a.host_list[out_pos] = pos;
-    a.host_vals[out_pos] = v;
-    ++out_pos;
+    // A listed position was touched: it is in the table.
+    list_store(a.out, out_pos++, pos, acc[medium_find(keys, pos)]);
   }
-  if (t == THREADS - 1) {
-    *a.count = sums[t];
-    *a.host_count = sums[t];
-  }
+  if (t == 0) list_store_count(a.out, total);
 }
 
 static_assert(kMediumCols == 64 * kCompactThreads, "one listed word per thread");
@@ -1046,7 +963,7 @@ __device__ __forceinline__ void column_wise_small_body(const ColWiseSmallArgs& a
   __shared__ double s_y[kSmallColWiseRows];
   __shared__ double s_w[kSmallColWiseRows];
   __shared__ uint8_t keep_flag[kSmallLdsCols];
-  __shared__ int sums[kCompactThreads];
+  __shared__ int lds_waves[kCompactThreads / kWave];
   const int t = threadIdx.x;
   const int n = a.num_cols;
   const bool with_dots = a.w != nullptr;
@@ -1074,30 +991,15 @@ __device__ __forceinline__ void column_wise_small_body(const ColWiseSmallArgs& a
   const int e = min(n, b + per);
   int c = 0;
   for (int pos = b; pos < e; ++pos) c += keep_flag[pos];
-  sums[t] = c;
-  __syncthreads();
-  for (int off = 1; off < kCompactThreads; off <<= 1) {
-    const int v = t >= off ? sums[t - off] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  int out_pos = sums[t] - c;
+  int total;
+  int out_pos = scan_block_exclusive<kCompactThreads>(c, &total, lds_waves);
   for (int pos = b; pos < e; ++pos) {
     if (keep_flag[pos]) {
-      const double v = a.coefficient[pos];  // written above by this workgroup
-      a.list[out_pos] = pos;
-      a.vals_out[out_pos] = v;
-      a.host_list[out_pos] = pos;
-      a.host_vals[out_pos] = v;
       if (with_dots) a.host_dots[out_pos] = a.out2[pos];
-      ++out_pos;
+      list_store(a.out, out_pos++, pos, a.coefficient[pos]);  // written above by this workgroup
     }
   }
-  if (t == kCompactThreads - 1) {
-    *a.count = sums[t];
-    *a.host_count = sums[t];
-  }
+  if (t == 0) list_store_count(a.out, total);
 }
 
 __global__ __launch_bounds__(kCompactThreads) void column_wise_small_kernel(ColWiseSmallArgs a) {
@@ -1137,12 +1039,6 @@ __global__ __launch_bounds__(kCompactThreads) void list_dots_medium_kernel(ListD
 // first-write rule as row_wise_update_kernel. Columns with more than
 // kMaxColumnHits filtered entries fall back to repeated minimum selection.
 constexpr int kMaxColumnHits = 32;  // = DeviceLp::kColumnKernelMaxColumnLength
-
-__device__ __forceinline__ double row_wise_accumulate(double acc, bool first, double v,
-                                                      int algorithm) {
-  if (!first) return acc + v;
-  return algorithm == 2 ? 0.0 + v : v;  // AssignToZero then +=, or first assign
-}
 
 // Per-column accumulation of the row-wise update row from the CSC copy:
 // k_of(r) = list position of row r, or -1 if r is not filtered. The hits are
@@ -1207,25 +1103,6 @@ __device__ __forceinline__ double column_hits_accumulate(int64_t s, int64_t e,
   return acc;
 }
 
-// The update-row write rule per algorithm (update_row.cc:196-280); returns
-// whether the position is listed.
-__device__ __forceinline__ bool row_wise_store(int algorithm, bool touched, bool rel, double acc,
-                                               double drop_tolerance, double* coefficient,
-                                               int col) {
-  bool listed;
-  if (algorithm == 0) {
-    listed = touched && rel && fabs(acc) > drop_tolerance;
-    if (listed) coefficient[col] = acc;
-  } else if (algorithm == 1) {
-    listed = touched && rel && fabs(acc) > drop_tolerance;
-    if (touched) coefficient[col] = acc;
-  } else {
-    listed = rel && fabs(acc) > drop_tolerance;
-    coefficient[col] = touched ? acc : 0.0;
-  }
-  return listed;
-}
-
 __global__ __launch_bounds__(256) void row_wise_by_column_kernel(RowWiseColArgs a) {
   const int col = blockIdx.x * blockDim.x + threadIdx.x;
   if (col >= a.num_cols) return;
@@ -1245,7 +1122,7 @@ __device__ __forceinline__ void row_wise_small_by_column_body(const RowWiseSmall
   __shared__ int32_t s_pos[kSmallLdsCols];
   __shared__ double s_rho[kSmallLdsCols];
   __shared__ uint64_t rel[kSmallLdsCols / 64];
-  __shared__ int sums[kCompactThreads];
+  __shared__ int lds_waves[kCompactThreads / kWave];
   const int t = threadIdx.x;
   const int n = a.num_cols;
   for (int r = t; r < a.m; r += kCompactThreads) s_pos[r] = -1;
@@ -1261,7 +1138,6 @@ __device__ __forceinline__ void row_wise_small_by_column_body(const RowWiseSmall
   const int b = min(n, t * per);
   const int e = min(n, b + per);
   uint32_t listed_bits = 0;
-  int c = 0;
   for (int col = b; col < e; ++col) {
     bool touched = false;
     const double acc = column_hits_accumulate(a.starts[col], a.starts[col + 1], a.rows, a.vals,
@@ -1271,31 +1147,14 @@ __device__ __forceinline__ void row_wise_small_by_column_body(const RowWiseSmall
                                        a.coefficient, col);
     a.flags[col] = listed ? 1 : 0;
     listed_bits |= uint32_t(listed) << (col - b);
-    c += listed;
   }
-  sums[t] = c;
-  __syncthreads();
-  for (int off = 1; off < kCompactThreads; off <<= 1) {
-    const int v = t >= off ? sums[t - off] : 0;
-    __syncthreads();
-    sums[t] += v;
-    __syncthreads();
-  }
-  int out_pos = sums[t] - c;
+  int total;
+  int out_pos = scan_block_exclusive<kCompactThreads>(__popc(listed_bits), &total, lds_waves);
   for (int col = b; col < e; ++col) {
-    if ((listed_bits >> (col - b)) & 1u) {
-      const double v = a.coefficient[col];  // this thread's own store above
-      a.list[out_pos] = col;
-      a.list_vals[out_pos] = v;
-      a.host_list[out_pos] = col;
-      a.host_vals[out_pos] = v;
-      ++out_pos;
-    }
+    // This thread's own store above.
+    if ((listed_bits >> (col - b)) & 1u) list_store(a.out, out_pos++, col, a.coefficient[col]);
   }
-  if (t == kCompactThreads - 1) {
-    *a.count = sums[t];
-    *a.host_count = sums[t];
-  }
+  if (t == 0) list_store_count(a.out, total);
 }
 
 __global__ __launch_bounds__(kCompactThreads) void row_wise_small_by_column_kernel(
@@ -2136,20 +1995,16 @@ hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hi
   return hipGetLastError();
 }
 
-hipError_t compact_flags(const uint8_t* flags, int n, const double* coeff, int32_t* list,
-                         double* vals, int* count, int32_t* host_list, double* host_vals,
-                         int* host_count, const ScanState& st, hipStream_t s) {
-  compact_flags_kernel<<<scan_tiles(n), kScanThreads, 0, s>>>(
-      flags, n, coeff, list, vals, count, host_list, host_vals, host_count, st);
+hipError_t compact_flags(const uint8_t* flags, int n, const double* coeff, const ListOut& out,
+                         const ScanState& st, hipStream_t s) {
+  compact_flags_kernel<<<scan_tiles(n), kScanThreads, 0, s>>>(flags, n, coeff, out, st);
   return hipGetLastError();
 }
 
-hipError_t compact_small(const uint8_t* flags, int n, const double* coeff, int32_t* list,
-                         double* vals, int* count, int32_t* host_list, double* host_vals,
-                         int* host_count, hipStream_t s) {
+hipError_t compact_small(const uint8_t* flags, int n, const double* coeff, const ListOut& out,
+                         hipStream_t s) {
   if (n > kSmallCompactMax) return hipErrorInvalidValue;
-  compact_small_kernel<<<1, kCompactThreads, 0, s>>>(flags, n, coeff, list, vals, count,
-                                                     host_list, host_vals, host_count);
+  compact_small_kernel<<<1, kCompactThreads, 0, s>>>(flags, n, coeff, out);
   return hipGetLastError();
 }
 
