@@ -1,0 +1,95 @@
+/* TEST SUPPORT ONLY: one DeviceLp operation at a time, with inputs the caller
+ * chooses. Not part of the solver API of include/mi_lp.h.
+ *
+ * A mi_devop handle owns the matrix pair [A | I] (CSC and its transpose) and a
+ * DeviceLp of its own; there is no RevisedSimplex behind it. create() reads
+ * the MILP_* environment switches (DeviceLp::Init), so a test sets the
+ * environment first and creates the handle afterwards.
+ *
+ * The library exports one read-only table, mi_devop_table, instead of one
+ * function per call: the exported functions of libmi_lp.so stay exactly those
+ * of mi_lp.h. Every call returns 0, or non-zero with a message in
+ * last_error(h) (a failed create: last_error(NULL), per thread). No C++
+ * exception crosses this boundary.
+ *
+ * Preconditions are DeviceLp's own and are not checked here: filtered rows
+ * ascend and are in range, column indices are in range, vectors have m (rho,
+ * w, v) or N = n + m (rc, colbits, bound_diff, out) elements. */
+#ifndef MI_LP_DEVOP_H_
+#define MI_LP_DEVOP_H_
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct mi_devop mi_devop;
+
+/* DeviceLp::LastPaths: which kernels the last operations went through. */
+enum {
+  MI_DEVOP_ROW_NONE = 0,
+  MI_DEVOP_ROW_SMALL_SERIAL = 1,
+  MI_DEVOP_ROW_SMALL_SERIAL_256 = 2,
+  MI_DEVOP_ROW_SMALL_BY_COLUMN = 3,
+  MI_DEVOP_ROW_MEDIUM_DIRECT = 4,
+  MI_DEVOP_ROW_MEDIUM_BATCHED = 5,
+  MI_DEVOP_ROW_LIST = 6,
+  MI_DEVOP_ROW_FULL_ROWS = 7,
+  MI_DEVOP_ROW_CHUNK = 8,
+  MI_DEVOP_ROW_BY_COLUMN = 9,
+  MI_DEVOP_ROW_COLUMN_WISE_SMALL = 10,
+  MI_DEVOP_ROW_COLUMN_WISE_GENERAL = 11
+};
+enum { MI_DEVOP_COMPACT_NONE = 0, MI_DEVOP_COMPACT_SMALL = 1, MI_DEVOP_COMPACT_CHIP_WIDE = 2 };
+enum { MI_DEVOP_RATIO_NONE = 0, MI_DEVOP_RATIO_ONE_WORKGROUP = 1, MI_DEVOP_RATIO_TWO_KERNELS = 2 };
+
+typedef struct mi_devop_paths {
+  int32_t update_row;      /* MI_DEVOP_ROW_* of the last update row */
+  int32_t compact;         /* MI_DEVOP_COMPACT_* of that update row */
+  int32_t ratio;           /* MI_DEVOP_RATIO_* of the last dual ratio test */
+  int32_t ratio_tightened; /* it ran the tightening round */
+  int32_t list_mapped;     /* the last list also went to the mapped host mirrors */
+} mi_devop_paths;
+
+typedef struct mi_devop_api {
+  /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
+  mi_devop* (*create)(int device, int m, int n, const int64_t* col_starts,
+                      const int32_t* row_idx, const double* vals);
+  void (*destroy)(mi_devop* h);
+  const char* (*last_error)(const mi_devop* h);
+  /* which: DeviceLp::Mask (0 relevant, 1 basic, 2 not basic). */
+  int (*set_mask)(mi_devop* h, int which, const uint64_t* words, int num_words);
+  int (*set_list_mirror)(mi_devop* h, int on);
+  int (*set_small_batch)(mi_devop* h, int on);
+  int (*update_row_row_wise)(mi_devop* h, const int32_t* rows, int k, const double* rho,
+                             int algorithm, double drop);
+  /* relevant_entries is computed from the last relevant mask. w may be NULL. */
+  int (*update_row_column_wise)(mi_devop* h, const double* rho, double drop, const double* w);
+  /* positions / values hold N elements. */
+  int (*fetch_update_row)(mi_devop* h, int32_t* positions, double* values, int* count);
+  int (*read_coefficient)(mi_devop* h, int col, double* out);
+  int (*download_coefficients)(mi_devop* h, double* out);
+  int (*list_dots_over_update_row)(mi_devop* h, const double* v, double* out, int* count);
+  int (*list_dots)(mi_devop* h, const int32_t* cols, int n, const double* v, double* out);
+  int (*dual_begin)(mi_devop* h, const double* rc, const uint8_t* colbits,
+                    const double* bound_diff);
+  int (*dual_set_col_bits)(mi_devop* h, const int32_t* cols, const uint8_t* bits, int n);
+  /* col / coeff / rc hold N elements. */
+  int (*dual_ratio_candidates)(mi_devop* h, double sign, double threshold,
+                               double harris_tolerance, double minimum_delta,
+                               double variation_magnitude, int32_t* col, double* coeff,
+                               double* rc, int* count, int* list_count);
+  int (*dual_update_reduced_costs)(mi_devop* h, double mult, int leaving_col,
+                                   double leaving_value, int entering_col);
+  int (*dual_download_reduced_costs)(mi_devop* h, double* rc);
+  int (*last_paths)(mi_devop* h, mi_devop_paths* out);
+} mi_devop_api;
+
+extern const mi_devop_api mi_devop_table;
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MI_LP_DEVOP_H_ */

@@ -84,6 +84,30 @@ class DeviceLp : public DeviceSolver {
   void FetchUpdateRow(std::vector<int>* positions, std::vector<double>* values);
   // Reads coefficient_[col] of the last update row (non-listed positions).
   double ReadCoefficient(int col);
+  // All N coefficients in one copy (test support; not on a solve's path).
+  void DownloadCoefficients(std::vector<double>* out);
+
+  // Which kernels the last operations went through (read-only record for the
+  // operation-level tests: a case asserts the path it was written for).
+  enum UpdateRowPath {
+    kRowNone = 0, kRowSmallSerial, kRowSmallSerial256, kRowSmallByColumn, kRowMediumDirect,
+    kRowMediumBatched, kRowList, kRowFullRows, kRowChunk, kRowByColumn, kRowColumnWiseSmall,
+    kRowColumnWiseGeneral
+  };
+  enum CompactPath { kCompactNone = 0, kCompactSmall, kCompactChipWide };
+  enum RatioPath { kRatioNone = 0, kRatioOneWorkgroup, kRatioTwoKernels };
+  struct LastPaths {
+    int update_row = kRowNone;
+    int compact = kCompactNone;   // of the last update row
+    int ratio = kRatioNone;
+    bool ratio_tightened = false;
+    bool list_mapped = false;     // the last list also went to the mapped mirrors
+  };
+  LastPaths last_paths() const {
+    LastPaths p = paths_;
+    p.list_mapped = mapped_result_;
+    return p;
+  }
 
   // --- dots over the listed update-row columns ---------------------------
   // out[k] = a_{list[k]} . v (primal_edge_norms.cc:229-233).
@@ -538,6 +562,11 @@ class DeviceLp : public DeviceSolver {
   double* d_map_vals_ = nullptr;
   bool list_mirror_ = true;
   bool mapped_result_ = false;  // the last Compact wrote to h_map_
+  LastPaths paths_;
+  void RowPath(int path) {  // a new update row: its compaction (if any) follows
+    paths_.update_row = path;
+    paths_.compact = kCompactNone;
+  }
   // Small LPs (N <= kSmallLdsCols): the row-wise update row is one launch
   // (row_wise_small_kernel) reading its inputs, including the relevant mask,
   // from mapped host memory (MILP_SMALL_FUSED=off disables).

@@ -1087,6 +1087,7 @@ void DeviceLp::Compact(int n, int bound) {
   // The result also lands in mapped host memory (the readback is the sync):
   // always for small N.
   const bool mirror = list_mirror_ || n <= milp_launch::kSmallCompactMax;
+  paths_.compact = n <= milp_launch::kSmallCompactMax ? kCompactSmall : kCompactChipWide;
   if (n <= milp_launch::kSmallCompactMax) {
     // One workgroup: flags -> list + coefficients + count in a single launch.
     Check(milp_launch::compact_small(d_flags_, n, d_coeff_, ListOutput(mirror), S(stream_)),
@@ -1128,6 +1129,7 @@ void DeviceLp::UpdateRowColumnWise(const std::vector<double>& rho, double drop,
     UpdateRowColumnWiseSmall(rho, drop, relevant_entries, w);
     return;
   }
+  RowPath(kRowColumnWiseGeneral);
   std::memcpy(h_pin_d_, rho.data(), m_ * sizeof(double));
   Upload(d_vec_m_, h_pin_d_, m_ * sizeof(double));
   if (w != nullptr) {
@@ -1167,6 +1169,7 @@ void DeviceLp::UpdateRowColumnWise(const std::vector<double>& rho, double drop,
 void DeviceLp::UpdateRowColumnWiseSmall(const std::vector<double>& rho, double drop,
                                         int64_t relevant_entries,
                                         const std::vector<double>* w) {
+  RowPath(kRowColumnWiseSmall);
   if (small_inflight_) Synchronize();
   std::memcpy(h_small_y_, rho.data(), m_ * sizeof(double));
   if (w != nullptr) {
@@ -1263,6 +1266,7 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
     // The mapped mirrors as Compact writes them: always for small N.
     const bool mirror = list_mirror_ || n_total_ <= milp_launch::kSmallCompactMax;
     const milp_kernels::RowWiseListArgs l{a, ListOutput(mirror)};
+    RowPath(kRowList);
     BeginKernel(id);
     Check(milp_launch::row_wise_list(l, static_cast<int>(entries), S(stream_)), "rowwise list");
     // The CSR entries, the rows and multipliers, the list slots (their count
@@ -1275,6 +1279,7 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
   BeginKernel(id);
   if (all_full) {
     // Full rows: a thread per column reads each row's entry directly.
+    RowPath(kRowFullRows);
     NextRowTag();
     Check(milp_launch::tag_rows(d_rows, k, row_tag_, d_row_tag_, d_row_pos_, S(stream_)),
           "tag rows");
@@ -1302,10 +1307,12 @@ void DeviceLp::UpdateRowRowWise(const std::vector<int>& filtered_rows,
   }
   if (k <= rowwise_chunk_max_rows_ || max_col_len_ > kColumnKernelMaxColumnLength) {
     // Few rows: workgroups own column chunks and merge the rows in order.
+    RowPath(kRowChunk);
     Check(milp_launch::row_wise_update(a, S(stream_)), "rowwise");
   } else {
     // Many rows: one thread per column gathers its filtered entries from the
     // CSC copy (same arithmetic, same order).
+    RowPath(kRowByColumn);
     NextRowTag();
     Check(milp_launch::tag_rows(d_rows, k, row_tag_, d_row_tag_, d_row_pos_, S(stream_)),
           "tag rows");
@@ -1345,6 +1352,7 @@ void DeviceLp::UpdateRowRowWiseSmall(const std::vector<int>& filtered_rows,
   std::memcpy(h_small_mask_, h_masks_[kRelevant].data(), mask_words_ * sizeof(uint64_t));
   const int id = algorithm == 0 ? MI_K_SINGLE_ROW : MI_K_UPDATE_ROW;
   if (!serial) {
+    RowPath(kRowSmallByColumn);
     milp_kernels::RowWiseSmallColArgs c{};
     c.starts = d_starts_;
     c.rows = d_rows_;
@@ -1382,6 +1390,9 @@ void DeviceLp::UpdateRowRowWiseSmall(const std::vector<int>& filtered_rows,
   a.drop_tolerance = drop;
   a.algorithm = algorithm;
   a.out = ListOutput(true);
+  // LaunchSmall batches only outside the dual device mode.
+  RowPath(medium_ ? (small_batch_ && !dual_ready_ ? kRowMediumBatched : kRowMediumDirect)
+                  : (small_threads_ == 256 ? kRowSmallSerial256 : kRowSmallSerial));
   BeginKernel(id);
   LaunchSmall(medium_ ? milp_kernels::kMediumRowWise : milp_kernels::kSmallRowWise, a);
   // Rows and multipliers, the CSR entries, N-sized flags/coefficients, the list.
@@ -1474,6 +1485,16 @@ void DeviceLp::CopyHost(void* dst, const void* src, size_t bytes) {
   ParallelRanges(static_cast<int64_t>(bytes), 1 << 18, 4096, [&](int, int64_t b, int64_t e) {
     std::memcpy(static_cast<char*>(dst) + b, static_cast<const char*>(src) + b, e - b);
   });
+}
+
+void DeviceLp::DownloadCoefficients(std::vector<double>* out) {
+  if (!shards_.empty()) throw DeviceError("DownloadCoefficients: not with column shards");
+  out->resize(n_total_);
+  if (n_total_ == 0) return;
+  // The batched small launches run on the batcher's stream: waited for first.
+  WaitStream();
+  Download(h_pin_d_, d_coeff_, n_total_ * sizeof(double));
+  std::memcpy(out->data(), h_pin_d_, n_total_ * sizeof(double));
 }
 
 double DeviceLp::ReadCoefficient(int col) {
@@ -1880,6 +1901,8 @@ void DeviceLp::DualRatioCandidates(double sign, double threshold, double harris_
   // copy: this one keeps its candidates on the device.
   sel.host_cap = std::max(0, tighten_min_candidates_);
   BeginKernel(MI_K_DUAL_RATIO);
+  paths_.ratio = bound <= dual_one_wg_max_ ? kRatioOneWorkgroup : kRatioTwoKernels;
+  paths_.ratio_tightened = false;
   if (bound <= dual_one_wg_max_) {
     // A short list: both passes in one workgroup, no tile chain.
     Check(milp_launch::dual_ratio_one_wg(a, sel, S(stream_)), "dual ratio one workgroup");
@@ -1896,6 +1919,7 @@ void DeviceLp::DualRatioCandidates(double sign, double threshold, double harris_
     if (k1 > bound || h_dual_counts_[1] > bound) {
       throw DeviceError("dual ratio test: bad counts");
     }
+    paths_.ratio_tightened = true;
     BeginKernel(MI_K_DUAL_RATIO);
     if (tighten_sort_) {
       Check(milp_launch::dual_ratio_keys(a, d_slots_, k1, d_keys_in_, S(stream_)), "keys");

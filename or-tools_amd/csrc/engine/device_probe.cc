@@ -1,0 +1,239 @@
+// TEST SUPPORT ONLY (include/mi_lp_devop.h): one thin call per public
+// DeviceLp method, so that a test can run a single device operation on inputs
+// it chooses. A handle owns its CompactSparseMatrix pair and its DeviceLp;
+// there is no RevisedSimplex behind it.
+#include <cstring>
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "../../../include/mi_lp_devop.h"
+#include "device_lp.h"
+#include "lp_data.h"
+
+struct mi_devop {
+  milp::CompactSparseMatrix csc;  // [A | I]
+  milp::CompactSparseMatrix csr;  // its transpose
+  milp::DeviceLp dev;
+  std::vector<uint64_t> relevant;  // the last kRelevant mask
+  std::string error;
+};
+
+namespace {
+
+thread_local std::string g_create_error;
+
+// Runs fn; a DeviceError (or any other exception) becomes a non-zero return
+// and the handle's message.
+template <typename Fn>
+int Guard(mi_devop* h, Fn fn) {
+  try {
+    fn();
+    return 0;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+  } catch (...) {
+    h->error = "unknown exception";
+  }
+  return 1;
+}
+
+mi_devop* Create(int device, int m, int n, const int64_t* col_starts, const int32_t* row_idx,
+                 const double* vals) {
+  mi_devop* h = nullptr;
+  try {
+    h = new mi_devop();
+    h->csc.PopulateFromSparseMatrixAndAddSlacks(m, n, col_starts, row_idx, vals);
+    h->csr.PopulateFromTranspose(h->csc);
+    h->dev.Init(device);
+    h->dev.UploadMatrix(h->csc, h->csr);
+    h->relevant.assign((h->csc.num_cols() + 63) / 64, ~0ull);
+    return h;
+  } catch (const std::exception& e) {
+    g_create_error = e.what();
+  } catch (...) {
+    g_create_error = "unknown exception";
+  }
+  try {
+    delete h;
+  } catch (...) {
+  }
+  return nullptr;
+}
+
+void Destroy(mi_devop* h) {
+  try {
+    delete h;
+  } catch (...) {
+  }
+}
+
+const char* LastError(const mi_devop* h) {
+  return h != nullptr ? h->error.c_str() : g_create_error.c_str();
+}
+
+int SetMask(mi_devop* h, int which, const uint64_t* words, int num_words) {
+  return Guard(h, [&] {
+    if (which < 0 || which >= milp::DeviceLp::kNumMasks) throw milp::DeviceError("bad mask");
+    h->dev.SetMask(static_cast<milp::DeviceLp::Mask>(which), words, num_words);
+    if (which == milp::DeviceLp::kRelevant) h->relevant.assign(words, words + num_words);
+  });
+}
+
+int SetListMirror(mi_devop* h, int on) {
+  return Guard(h, [&] { h->dev.SetListMirror(on != 0); });
+}
+
+int SetSmallBatch(mi_devop* h, int on) {
+  return Guard(h, [&] { h->dev.SetSmallBatch(on != 0); });
+}
+
+int UpdateRowRowWise(mi_devop* h, const int32_t* rows, int k, const double* rho, int algorithm,
+                     double drop) {
+  return Guard(h, [&] {
+    const std::vector<int> filtered(rows, rows + k);
+    const std::vector<double> r(rho, rho + h->csc.num_rows());
+    h->dev.UpdateRowRowWise(filtered, r, algorithm, drop);
+  });
+}
+
+int UpdateRowColumnWise(mi_devop* h, const double* rho, double drop, const double* w) {
+  return Guard(h, [&] {
+    const int m = h->csc.num_rows();
+    const std::vector<double> r(rho, rho + m);
+    int64_t relevant_entries = 0;
+    for (int c = 0; c < h->csc.num_cols(); ++c) {
+      if (h->relevant[c >> 6] >> (c & 63) & 1) relevant_entries += h->csc.ColumnNumEntries(c);
+    }
+    if (w != nullptr) {
+      const std::vector<double> wv(w, w + m);
+      h->dev.UpdateRowColumnWise(r, drop, relevant_entries, &wv);
+    } else {
+      h->dev.UpdateRowColumnWise(r, drop, relevant_entries);
+    }
+  });
+}
+
+int FetchUpdateRow(mi_devop* h, int32_t* positions, double* values, int* count) {
+  return Guard(h, [&] {
+    std::vector<int> p;
+    std::vector<double> v;
+    h->dev.FetchUpdateRow(&p, &v);
+    *count = static_cast<int>(p.size());
+    if (!p.empty()) {
+      std::memcpy(positions, p.data(), p.size() * sizeof(int32_t));
+      std::memcpy(values, v.data(), v.size() * sizeof(double));
+    }
+  });
+}
+
+int ReadCoefficient(mi_devop* h, int col, double* out) {
+  return Guard(h, [&] { *out = h->dev.ReadCoefficient(col); });
+}
+
+int DownloadCoefficients(mi_devop* h, double* out) {
+  return Guard(h, [&] {
+    std::vector<double> v;
+    h->dev.DownloadCoefficients(&v);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(double));
+  });
+}
+
+int ListDotsOverUpdateRow(mi_devop* h, const double* v, double* out, int* count) {
+  return Guard(h, [&] {
+    const std::vector<double> vv(v, v + h->csc.num_rows());
+    std::vector<double> o;
+    h->dev.ListDotsOverUpdateRow(vv, &o);
+    *count = static_cast<int>(o.size());
+    if (!o.empty()) std::memcpy(out, o.data(), o.size() * sizeof(double));
+  });
+}
+
+int ListDots(mi_devop* h, const int32_t* cols, int n, const double* v, double* out) {
+  return Guard(h, [&] {
+    const std::vector<int> c(cols, cols + n);
+    const std::vector<double> vv(v, v + h->csc.num_rows());
+    std::vector<double> o;
+    h->dev.ListDots(c, vv, &o);
+    if (!o.empty()) std::memcpy(out, o.data(), o.size() * sizeof(double));
+  });
+}
+
+int DualBegin(mi_devop* h, const double* rc, const uint8_t* colbits, const double* bound_diff) {
+  return Guard(h, [&] {
+    const int n = h->csc.num_cols();
+    h->dev.DualBegin(std::vector<double>(rc, rc + n), std::vector<uint8_t>(colbits, colbits + n),
+                     std::vector<double>(bound_diff, bound_diff + n));
+  });
+}
+
+int DualSetColBits(mi_devop* h, const int32_t* cols, const uint8_t* bits, int n) {
+  return Guard(h, [&] {
+    h->dev.DualSetColBits(std::vector<int32_t>(cols, cols + n),
+                          std::vector<uint8_t>(bits, bits + n));
+  });
+}
+
+int DualRatioCandidates(mi_devop* h, double sign, double threshold, double harris_tolerance,
+                        double minimum_delta, double variation_magnitude, int32_t* col,
+                        double* coeff, double* rc, int* count, int* list_count) {
+  return Guard(h, [&] {
+    milp::DeviceLp::DualCandidates c;
+    h->dev.DualRatioCandidates(sign, threshold, harris_tolerance, minimum_delta,
+                               variation_magnitude, &c);
+    *count = static_cast<int>(c.col.size());
+    *list_count = c.list_count;
+    if (!c.col.empty()) {
+      std::memcpy(col, c.col.data(), c.col.size() * sizeof(int32_t));
+      std::memcpy(coeff, c.coeff.data(), c.coeff.size() * sizeof(double));
+      std::memcpy(rc, c.rc.data(), c.rc.size() * sizeof(double));
+    }
+  });
+}
+
+int DualUpdateReducedCosts(mi_devop* h, double mult, int leaving_col, double leaving_value,
+                           int entering_col) {
+  return Guard(h, [&] {
+    h->dev.DualUpdateReducedCosts(mult, leaving_col, leaving_value, entering_col);
+  });
+}
+
+int DualDownloadReducedCosts(mi_devop* h, double* rc) {
+  return Guard(h, [&] {
+    std::vector<double> v;
+    h->dev.DualDownloadReducedCosts(&v);
+    if (!v.empty()) std::memcpy(rc, v.data(), v.size() * sizeof(double));
+  });
+}
+
+int LastPaths(mi_devop* h, mi_devop_paths* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastPaths p = h->dev.last_paths();
+    out->update_row = p.update_row;
+    out->compact = p.compact;
+    out->ratio = p.ratio;
+    out->ratio_tightened = p.ratio_tightened ? 1 : 0;
+    out->list_mapped = p.list_mapped ? 1 : 0;
+  });
+}
+
+static_assert(int{MI_DEVOP_ROW_COLUMN_WISE_GENERAL} == int{milp::DeviceLp::kRowColumnWiseGeneral} &&
+                  int{MI_DEVOP_ROW_LIST} == int{milp::DeviceLp::kRowList} &&
+                  int{MI_DEVOP_COMPACT_CHIP_WIDE} == int{milp::DeviceLp::kCompactChipWide} &&
+                  int{MI_DEVOP_RATIO_TWO_KERNELS} == int{milp::DeviceLp::kRatioTwoKernels},
+              "mi_lp_devop.h restates DeviceLp's path enums");
+
+}  // namespace
+
+extern "C" const mi_devop_api mi_devop_table = {
+    Create,           Destroy,
+    LastError,        SetMask,
+    SetListMirror,    SetSmallBatch,
+    UpdateRowRowWise, UpdateRowColumnWise,
+    FetchUpdateRow,   ReadCoefficient,
+    DownloadCoefficients, ListDotsOverUpdateRow,
+    ListDots,         DualBegin,
+    DualSetColBits,   DualRatioCandidates,
+    DualUpdateReducedCosts, DualDownloadReducedCosts,
+    LastPaths,
+};
