@@ -411,6 +411,18 @@ class DeviceLp : public DeviceSolver {
   void TriReserve(TriBuffer* b, size_t bytes);
   void PrepareTriContext(int slot, int rows, int pos);
   milp_kernels::TriSolveArgs TriArgs(const TriSchedule& s, const TriContext& c) const;
+  // One solve's staging: x[first, rows) goes in, the outputs up to row `top`
+  // are computed, x[first, top] comes back.
+  struct TriRun {
+    int rows = 0, first = 0, top = -1;
+    double bytes = 0.0;   // algorithmic bytes of the solve
+    bool trivial = true;  // nothing to compute: the input is the result
+  };
+  TriRun TriBegin(TriKind kind, const TriSchedule& s, const double* x) const;
+  void TriStageIn(const TriContext& c, const double* x, const TriRun& run);
+  void TriTakeResult(const TriContext& c, const TriRun& run, double* x);
+  void TriAccountOffThread(int id, const TriContext& c, const TriRun& run, bool timed);
+  bool TriSyncFreeFits(const TriSchedule& s) const;
   void TriCopyIn(const TriSchedule& s, const TriContext& c);
   void TriCopyOut(const TriSchedule& s, const TriContext& c);
   void EnqueueTriKernels(const TriSchedule& s, const milp_kernels::TriSolveArgs& a,
@@ -742,12 +754,8 @@ class DeviceLp : public DeviceSolver {
   // compute: the input is the result).
   struct AsyncU {
     bool active = false;
-    bool trivial = false;
     bool timed = false;  // events recorded around the launch
-    int rows = 0;
-    int first = 0;
-    int top = 0;
-    double bytes = 0.0;
+    TriRun run;
   };
   AsyncU async_u_;
   // MILP_SPEC_FLIP=0 turns the speculative flip FTRAN (lu.h) off; read by the

@@ -170,8 +170,9 @@ void DeviceLp::Init(int device) {
   }
   if (const char* v = std::getenv("MILP_DEVICE_SOLVE_MIN_ROWS")) tri_min_rows_ = std::atoi(v);
   if (const char* v = std::getenv("MILP_TRI_WIDE")) tri_wide_level_ = std::atoi(v);
-  // MILP_TRI_GRAPH=0: launch the plan kernel by kernel instead of replaying
-  // a captured graph; MILP_TRI_TAU=0: the tau worker keeps the host loop.
+  // MILP_TRI_GRAPH=1: replay the plan as a captured graph instead of launching
+  // it kernel by kernel (off by default); MILP_TRI_TAU=0: the tau worker keeps
+  // the host loop.
   if (const char* v = std::getenv("MILP_TRI_GRAPH")) tri_graph_ = std::atoi(v) != 0;
   if (const char* v = std::getenv("MILP_TRI_TAU")) tri_tau_ = std::atoi(v) != 0;
   if (const char* v = std::getenv("MILP_TRI_MAPPED")) tri_mapped_ = std::atoi(v) != 0;

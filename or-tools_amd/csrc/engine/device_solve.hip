@@ -503,6 +503,14 @@ void DeviceLp::TriCopyOut(const TriSchedule& s, const TriContext& c) {
         "D2H");
 }
 
+// Every workgroup of the sync-free plan's widest launch resident at once
+// (for a pair, 2 x 512 workgroups of 256 at most: 4 per CU of the 8 the
+// kernel's registers allow), and deep enough to beat a few level launches.
+bool DeviceLp::TriSyncFreeFits(const TriSchedule& s) const {
+  return s.max_wide_run <= milp_kernels::kTriSyncFreeMaxWork &&
+         s.levels >= tri_syncfree_min_levels_;
+}
+
 void DeviceLp::EnqueueTriKernels(const TriSchedule& s, const milp_kernels::TriSolveArgs& a,
                                  void* stream) {
   // The single-launch kernel pays a cross-workgroup hand-off per level; a
@@ -514,8 +522,7 @@ void DeviceLp::EnqueueTriKernels(const TriSchedule& s, const milp_kernels::TriSo
           "tri persistent");
     return;
   }
-  if (tri_syncfree_ && a.clock == nullptr && s.max_wide_run <= milp_kernels::kTriSyncFreeMaxWork &&
-      s.levels >= tri_syncfree_min_levels_) {
+  if (tri_syncfree_ && a.clock == nullptr && TriSyncFreeFits(s)) {
     Check(milp_launch::tri_transpose_lower_syncfree(a, s.runs.data(),
                                                     static_cast<int>(s.runs.size() / 3),
                                                     Stream(stream)),
@@ -787,7 +794,7 @@ bool DeviceLp::TriPrepare(int which, const TriangularMatrix& t, uint64_t key, in
     if (c.stream == nullptr) PrepareTriContext(slot, nc, 1);
     if (s.key != key) {
       // An asynchronous U solve reads the schedule being replaced.
-      if (which == kTriU && async_u_.active && !async_u_.trivial) {
+      if (which == kTriU && async_u_.active && !async_u_.run.trivial) {
         (void)hipStreamSynchronize(Stream(tri_ctx_[3].stream));
       }
       DeviceOp("tri build");
@@ -871,6 +878,68 @@ bool DeviceLp::TriPrepare(int which, const TriangularMatrix& t, uint64_t key, in
   return true;
 }
 
+// What the solve of x computes. U (sparse.cc:908-912): the host loop starts
+// at the last non-zero; the other loops run over every column (outputs below
+// their start receive nothing).
+DeviceLp::TriRun DeviceLp::TriBegin(TriKind kind, const TriSchedule& s, const double* x) const {
+  TriRun run;
+  run.rows = s.rows;
+  run.first = s.first_col;
+  run.top = s.rows - 1;
+  if (kind == TriKind::kUpperT || kind == TriKind::kLowerT) {
+    while (run.top >= run.first && x[run.top] == 0.0) --run.top;
+  }
+  if (run.top < run.first) return run;
+  const double rows = s.rows_upto[run.top + 1] - s.rows_upto[run.first];
+  if (rows == 0) return run;  // identity part only
+  const double entries =
+      static_cast<double>(s.entries_upto[run.top + 1] - s.entries_upto[run.first]);
+  // Per computed output: its record (row, count: 8 B), its value in and out
+  // (16 B), the diagonal (8 B) unless unit; per entry: position and value
+  // (12 B) and the value it reads (8 B). The permutes in and out: 8 B in, 8 B
+  // out and the 4-B row index per position, both ways.
+  run.bytes = rows * (24.0 + (s.ones ? 0.0 : 8.0)) + entries * 20.0 + double(s.pos) * 20.0 +
+              rows * 20.0;
+  run.trivial = false;
+  return run;
+}
+
+// Outputs c >= first read rows >= first only: x[first, rows) goes into the
+// context's staging, with the top row (the zero-copy plan reads it from the
+// word after the values, the copying one from h_top) and, in the next word,
+// the cleared failure flag of the sync-free kernels.
+void DeviceLp::TriStageIn(const TriContext& c, const double* x, const TriRun& run) {
+  CopyHost(c.h_x + run.first, x + run.first, size_t(run.rows - run.first) * sizeof(double));
+  *c.h_top = run.top;
+  int* words = reinterpret_cast<int*>(c.h_x + run.rows);
+  words[0] = run.top;
+  words[1] = 0;
+}
+
+// After the stream's wait: x[first, top] back from the staging, unless a
+// bounded wait of the solve's kernels ran out.
+void DeviceLp::TriTakeResult(const TriContext& c, const TriRun& run, double* x) {
+  const int* words = reinterpret_cast<const int*>(c.h_x + run.rows);
+  if (*static_cast<const volatile int*>(words + 1) != 0) {
+    throw DeviceError("triangular solve: dependency wait timed out");
+  }
+  CopyHost(x + run.first, c.h_x + run.first, size_t(run.top - run.first + 1) * sizeof(double));
+}
+
+// A finished solve that did not run between BeginKernel and EndKernel (the
+// tau worker's, the asynchronous one): its counters, and with `timed` the
+// time between the context's two events.
+void DeviceLp::TriAccountOffThread(int id, const TriContext& c, const TriRun& run, bool timed) {
+  stats_.launches[id] += 1;
+  stats_.algorithmic_bytes[id] += run.bytes;
+  if (!timed) return;
+  float ms = 0.0f;
+  Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(c.ev[0]),
+                            reinterpret_cast<hipEvent_t>(c.ev[1])),
+        "ev time");
+  stats_.device_ms[id] += ms;
+}
+
 bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
                         std::vector<double>* x) {
   // The solver's thread (slot 0) or the factorization's tau worker (slot 1).
@@ -886,36 +955,13 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
   DeviceOp(which == kTriU ? (slot == 0 ? "tri U enter" : "tri U enter (slot 1)")
                           : (slot == 0 ? "tri L enter" : "tri L enter (slot 1)"));
   if (!TriPrepare(which, t, key, slot, *x)) return false;
-  const int nc = t.num_cols();
   TriContext& c = tri_ctx_[slot];
   TriSchedule& s = tri_sched_[which];
-  double* xv = x->data();
-  const int fni = s.first_col;
-  // U (sparse.cc:908-912): the host loop starts at the last non-zero; the
-  // L loop runs over every column (outputs below its start receive nothing).
-  int top = nc - 1;
-  if (kind == TriKind::kUpperT || kind == TriKind::kLowerT) {
-    while (top >= fni && xv[top] == 0.0) --top;
-    if (top < fni) return true;
-  }
-  if (s.rows_upto[top + 1] - s.rows_upto[fni] == 0) return true;  // identity part only
-  // Outputs c >= fni read rows >= fni only: x[fni..nc) in and out.
-  const size_t in = size_t(nc - fni);
+  const TriRun run = TriBegin(kind, s, x->data());
+  if (run.trivial) return true;
   FtranTimer ft(kFtDevCopyIn);
-  CopyHost(c.h_x + fni, xv + fni, in * sizeof(double));
+  TriStageIn(c, x->data(), run);
   ft.Lap(kFtDevRun);
-  *c.h_top = top;
-  int* h_words = reinterpret_cast<int*>(c.h_x + nc);
-  h_words[0] = top;  // zero-copy plan reads it here
-  h_words[1] = 0;    // the sync-free kernel's failure word
-  const double rows = s.rows_upto[top + 1] - s.rows_upto[fni];
-  const double entries = static_cast<double>(s.entries_upto[top + 1] - s.entries_upto[fni]);
-  // Per computed output: its record (row, count: 8 B), its value in and out
-  // (16 B), the diagonal (8 B) unless unit; per entry: position and value
-  // (12 B) and the value it reads (8 B). The permutes in and out: 8 B in, 8 B
-  // out and the 4-B row index per position, both ways.
-  const double bytes = rows * (24.0 + (s.ones ? 0.0 : 8.0)) + entries * 20.0 +
-                       double(s.pos) * 20.0 + rows * 20.0;
   if (slot == 0 && which == kTriU && tri_debug_left_ > 0) {
     // MILP_TRI_DEBUG=k: per-level wall clock of the first k U solves after
     // each schedule build (level plan), printed with the level widths.
@@ -930,7 +976,7 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
     TriCopyIn(s, c);
     BeginKernel(id);
     EnqueueTriKernels(s, a, c.stream);
-    EndKernel(id, bytes);
+    EndKernel(id, run.bytes);
     TriCopyOut(s, c);
     // The armed MPF right-pool append reads the FTRAN vector before it is
     // overwritten below, as on the normal path.
@@ -946,7 +992,7 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
                  "[tri] U: rows %d work %d levels %d segments %zu top %d entries/row max %d "
                  ">4 %d >16 %d >64 %d | L: work %d levels %d entries/row max %d >4 %d >16 %d "
                  ">64 %d; U per level (us/width):",
-                 nc, s.work, s.levels, s.segments.size() / 2, top, s.max_entries,
+                 run.rows, s.work, s.levels, s.segments.size() / 2, run.top, s.max_entries,
                  s.rows_over[0], s.rows_over[1], s.rows_over[2], l.work, l.levels,
                  l.max_entries, l.rows_over[0], l.rows_over[1], l.rows_over[2]);
     for (int lv = 0; lv < s.levels; ++lv) {
@@ -976,7 +1022,7 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
       EnqueueTriKernels(s, TriArgs(s, c), c.stream);
     }
     if (slot == 0) {
-      EndKernel(id, bytes);
+      EndKernel(id, run.bytes);
     } else if (Timed(id)) {
       Check(hipEventRecord(reinterpret_cast<hipEvent_t>(c.ev[1]), Stream(c.stream)), "ev");
     }
@@ -985,24 +1031,11 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
     DeviceOp("tri sync");
     Check(hipStreamSynchronize(Stream(c.stream)), "sync");
     DeviceOp("tri sync done");
-    if (slot != 0) {
-      // The worker's own counters (its id is written by this thread only).
-      stats_.launches[id] += 1;
-      stats_.algorithmic_bytes[id] += bytes;
-      if (Timed(id)) {
-        float ms = 0.0f;
-        Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(c.ev[0]),
-                                  reinterpret_cast<hipEvent_t>(c.ev[1])),
-              "ev time");
-        stats_.device_ms[id] += ms;
-      }
-    }
-  }
-  if (*static_cast<volatile int*>(h_words + 1) != 0) {
-    throw DeviceError("triangular solve: dependency wait timed out");
+    // The worker's own counters (its id is written by this thread only).
+    if (slot != 0) TriAccountOffThread(id, c, run, Timed(id));
   }
   ft.Lap(kFtDevCopyOut);
-  CopyHost(xv + fni, c.h_x + fni, size_t(top - fni + 1) * sizeof(double));
+  TriTakeResult(c, run, x->data());
   return true;
 }
 
@@ -1021,44 +1054,23 @@ bool DeviceLp::SolvePair(TriKind kind, const TriangularMatrix& t, uint64_t key,
   if (!TriPrepare(kTriU, t, key, 0, *x0)) return false;
   if (static_cast<int>(x1->size()) < t.num_cols()) return false;
   TriSchedule& s = tri_sched_[kTriU];
-  // Both vectors' workgroups resident at once: 2 x 512 workgroups of 256
-  // at most, 4 per CU of the 8 the kernel's registers allow.
-  if (s.max_wide_run > milp_kernels::kTriSyncFreeMaxWork || s.levels < tri_syncfree_min_levels_) {
-    return false;
-  }
-  const int nc = t.num_cols();
-  const int fni = s.first_col;
+  if (!TriSyncFreeFits(s)) return false;
   {
     std::lock_guard<std::mutex> lock(tri_mu_);
-    PrepareTriContext(2, nc, s.pos);
+    PrepareTriContext(2, t.num_cols(), s.pos);
   }
   TriContext& c0 = tri_ctx_[0];
   TriContext& c1 = tri_ctx_[2];
   std::vector<double>* xs[2] = {x0, x1};
   TriContext* cs[2] = {&c0, &c1};
-  int tops[2];
-  double bytes = 0.0;
+  TriRun runs[2];
   for (int v = 0; v < 2; ++v) {
-    const double* xv = xs[v]->data();
-    int top = nc - 1;
-    while (top >= fni && xv[top] == 0.0) --top;
     // A vector with nothing to compute (only the identity part) is solved
     // alone by the caller's single path.
-    if (top < fni || s.rows_upto[top + 1] - s.rows_upto[fni] == 0) return false;
-    tops[v] = top;
-    const double rows = s.rows_upto[top + 1] - s.rows_upto[fni];
-    const double entries = static_cast<double>(s.entries_upto[top + 1] - s.entries_upto[fni]);
-    bytes += rows * (24.0 + (s.ones ? 0.0 : 8.0)) + entries * 20.0 + double(s.pos) * 20.0 +
-             rows * 20.0;
+    runs[v] = TriBegin(kind, s, xs[v]->data());
+    if (runs[v].trivial) return false;
   }
-  const size_t in = size_t(nc - fni);
-  for (int v = 0; v < 2; ++v) {
-    TriContext& c = *cs[v];
-    CopyHost(c.h_x + fni, xs[v]->data() + fni, in * sizeof(double));
-    int* words = reinterpret_cast<int*>(c.h_x + nc);
-    words[0] = tops[v];
-    words[1] = 0;
-  }
+  for (int v = 0; v < 2; ++v) TriStageIn(*cs[v], xs[v]->data(), runs[v]);
   milp_kernels::TriSolveArgs a = TriArgs(s, c0);
   a.x2 = static_cast<double*>(c1.x.ptr);
   a.y2 = static_cast<double*>(c1.y.ptr);
@@ -1070,19 +1082,11 @@ bool DeviceLp::SolvePair(TriKind kind, const TriangularMatrix& t, uint64_t key,
                                                   static_cast<int>(s.runs.size() / 3),
                                                   Stream(c0.stream), 2),
         "tri pair");
-  EndKernel(MI_K_TRI_SOLVE, bytes);
+  EndKernel(MI_K_TRI_SOLVE, runs[0].bytes + runs[1].bytes);
   g_overlap.Run();  // host work behind the device's
   DeviceOp("tri pair sync");
   Check(hipStreamSynchronize(Stream(c0.stream)), "sync");
-  for (int v = 0; v < 2; ++v) {
-    const int* words = reinterpret_cast<const int*>(cs[v]->h_x + nc);
-    if (*static_cast<const volatile int*>(words + 1) != 0) {
-      throw DeviceError("triangular solve: dependency wait timed out");
-    }
-  }
-  for (int v = 0; v < 2; ++v) {
-    CopyHost(xs[v]->data() + fni, cs[v]->h_x + fni, size_t(tops[v] - fni + 1) * sizeof(double));
-  }
+  for (int v = 0; v < 2; ++v) TriTakeResult(*cs[v], runs[v], xs[v]->data());
   return true;
 }
 
@@ -1095,27 +1099,13 @@ bool DeviceLp::StartAsyncU(const TriangularMatrix& t, uint64_t key, const std::v
   }
   DropAsyncU();
   if (!TriPrepare(kTriU, t, key, 3, x)) return false;
-  const int nc = t.num_cols();
   TriContext& c = tri_ctx_[3];
   TriSchedule& s = tri_sched_[kTriU];
-  const int fni = s.first_col;
-  int top = nc - 1;
-  while (top >= fni && x[top] == 0.0) --top;
+  async_u_.run = TriBegin(TriKind::kUpperT, s, x.data());
   async_u_.active = true;
-  async_u_.trivial = top < fni || s.rows_upto[top + 1] - s.rows_upto[fni] == 0;
-  if (async_u_.trivial) return true;
+  if (async_u_.run.trivial) return true;
   DeviceOp("tri U async enter");
-  CopyHost(c.h_x + fni, x.data() + fni, size_t(nc - fni) * sizeof(double));
-  int* h_words = reinterpret_cast<int*>(c.h_x + nc);
-  h_words[0] = top;
-  h_words[1] = 0;
-  const double rows = s.rows_upto[top + 1] - s.rows_upto[fni];
-  const double entries = static_cast<double>(s.entries_upto[top + 1] - s.entries_upto[fni]);
-  async_u_.bytes = rows * (24.0 + (s.ones ? 0.0 : 8.0)) + entries * 20.0 +
-                   double(s.pos) * 20.0 + rows * 20.0;
-  async_u_.rows = nc;
-  async_u_.first = fni;
-  async_u_.top = top;
+  TriStageIn(c, x.data(), async_u_.run);
   async_u_.timed = Timed(MI_K_TRI_SOLVE);
   if (async_u_.timed) {
     Check(hipEventRecord(reinterpret_cast<hipEvent_t>(c.ev[0]), Stream(c.stream)), "ev");
@@ -1130,31 +1120,18 @@ bool DeviceLp::StartAsyncU(const TriangularMatrix& t, uint64_t key, const std::v
 void DeviceLp::FinishAsyncU(std::vector<double>* x) {
   if (!async_u_.active) throw DeviceError("asynchronous U solve: none in flight");
   async_u_.active = false;
-  if (async_u_.trivial) return;
+  if (async_u_.run.trivial) return;
   TriContext& c = tri_ctx_[3];
   DeviceOp("tri U async sync");
   Check(hipStreamSynchronize(Stream(c.stream)), "sync");
-  stats_.launches[MI_K_TRI_SOLVE] += 1;
-  stats_.algorithmic_bytes[MI_K_TRI_SOLVE] += async_u_.bytes;
-  if (async_u_.timed && Timed(MI_K_TRI_SOLVE)) {
-    float ms = 0.0f;
-    Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(c.ev[0]),
-                              reinterpret_cast<hipEvent_t>(c.ev[1])),
-          "ev time");
-    stats_.device_ms[MI_K_TRI_SOLVE] += ms;
-  }
-  const int nc = async_u_.rows;
-  if (*reinterpret_cast<volatile int*>(reinterpret_cast<int*>(c.h_x + nc) + 1) != 0) {
-    throw DeviceError("triangular solve: dependency wait timed out");
-  }
-  const int fni = async_u_.first;
-  CopyHost(x->data() + fni, c.h_x + fni, size_t(async_u_.top - fni + 1) * sizeof(double));
+  TriAccountOffThread(MI_K_TRI_SOLVE, c, async_u_.run, async_u_.timed && Timed(MI_K_TRI_SOLVE));
+  TriTakeResult(c, async_u_.run, x->data());
 }
 
 void DeviceLp::DropAsyncU() {
   if (!async_u_.active) return;
   async_u_.active = false;
-  if (!async_u_.trivial && tri_ctx_[3].stream != nullptr) {
+  if (!async_u_.run.trivial && tri_ctx_[3].stream != nullptr) {
     (void)hipStreamSynchronize(Stream(tri_ctx_[3].stream));
   }
 }

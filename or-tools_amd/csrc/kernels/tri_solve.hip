@@ -12,7 +12,9 @@
 // one group at a time, then the 1-3 remaining products one by one, entries
 // taken from the end of the column. Computing x[c] from its entries in that
 // order gives Glop's bits, whatever the order in which the outputs are
-// computed, as long as every x[r] read is final.
+// computed, as long as every x[r] read is final. That order (and the
+// sequential one of the scatter loops restated as gathers) is written once,
+// in tri_eval.h; the kernels here load, wait and store around it.
 //
 // Layout (engine/device_solve.hip builds it once per factorization): the
 // outputs are listed by dependency level (level 0: no entries) and the
@@ -33,6 +35,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernel_args.h"
+#include "tri_eval.h"
 
 namespace milp_kernels {
 
@@ -65,102 +68,60 @@ __device__ __forceinline__ void tri_load(const TriSolveArgs& a, int k, int le, i
   r->d = a.diag != nullptr ? a.diag[kk] : 1.0;
 }
 
-// Entries of a long output (overflow arrays), in evaluation order, by batches
-// of 8 whose loads go out together.
-__device__ __forceinline__ double subtract_overflow(const TriSolveArgs& a, const double* y,
-                                                   double sum, int e, int end) {
-  for (; e + 7 < end; e += 8) {
-    double p[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) p[i] = a.ovf_value[e + i] * load_final(y, a.ovf_pos[e + i]);
-    sum -= p[0] + p[1] + p[2] + p[3];
-    sum -= p[4] + p[5] + p[6] + p[7];
-  }
-  for (; e + 3 < end; e += 4) {
-    sum -= a.ovf_value[e] * load_final(y, a.ovf_pos[e]) +
-           a.ovf_value[e + 1] * load_final(y, a.ovf_pos[e + 1]) +
-           a.ovf_value[e + 2] * load_final(y, a.ovf_pos[e + 2]) +
-           a.ovf_value[e + 3] * load_final(y, a.ovf_pos[e + 3]);
-  }
-  if (e < end) {
-    sum -= a.ovf_value[e] * load_final(y, a.ovf_pos[e]);
-    if (e + 1 < end) {
-      sum -= a.ovf_value[e + 1] * load_final(y, a.ovf_pos[e + 1]);
-      if (e + 2 < end) sum -= a.ovf_value[e + 2] * load_final(y, a.ovf_pos[e + 2]);
-    }
-  }
-  return sum;
+// Where an output's entries read their (final) values: y itself, at agent
+// scope (values written in the same launch are never read from a stale line).
+struct TriFinalValues {
+  const double* y;
+  __device__ __forceinline__ double operator()(int p) const { return load_final(y, p); }
+};
+
+// A scatter loop's own column (sparse.cc:792-846) skips a zero, which keeps
+// its bits and is not divided; consumers skip the columns whose final value
+// is zero, as the loop does (bit-identical except where value / diagonal
+// underflows to zero, which the loop would still scatter). tri_eval.h has
+// the rule.
+__device__ __forceinline__ double tri_divide(const TriSolveArgs& a, double sum, double d) {
+  return tri_finish(a.sequential != 0, a.diag != nullptr, sum, d);
 }
 
-// LowerSolve's order (sparse.cc:793-812 seen from one output): one
-// subtraction per entry in ascending column order, an entry whose value is
-// zero contributes nothing (the host skips that column). Loads by batches of 8.
-__device__ __forceinline__ double subtract_sequential(const TriSolveArgs& a, const double* y,
-                                                     double sum, int e, int end) {
-  for (; e < end; e += 8) {
-    double v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = e + i < end ? load_final(y, a.ovf_pos[e + i]) : 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if (e + i < end && v[i] != 0.0) sum -= v[i] * a.ovf_value[e + i];
-    }
-  }
-  return sum;
+// An output of at most 4 entries from its input `sum` and its entries' values.
+__device__ __forceinline__ double tri_short_output(const TriSolveArgs& a, double sum,
+                                                   const TriRec& r, double y0, double y1,
+                                                   double y2, double y3) {
+  return tri_divide(a, tri_short(a.sequential != 0, r.n, sum, r.v, y0, y1, y2, y3), r.d);
 }
 
-// A scatter loop's own column (sparse.cc:792-846): a zero is skipped, so it
-// keeps its bits and is not divided; anything else is divided by the
-// diagonal (nothing to do for a unit one). Consumers skip the columns whose
-// final value is zero, as the loop does (bit-identical except where value /
-// diagonal underflows to zero, which the loop would still scatter).
-__device__ __forceinline__ double tri_sequential_divide(const TriSolveArgs& a, double sum,
-                                                        double d) {
-  return (a.diag != nullptr && sum != 0.0) ? sum / d : sum;
-}
-
-// The output's value from its input `sum` and its entries (final values).
-__device__ __forceinline__ double tri_apply(const TriSolveArgs& a, const double* y, double sum,
+// The output's value from its input `sum` and its entries, whose values
+// (final) are read through `val`. A long output (overflow arrays) takes its
+// entries by windows of 8 whose loads go out together; every value being
+// final, a window folds whole.
+template <typename Val>
+__device__ __forceinline__ double tri_apply(const TriSolveArgs& a, const Val& val, double sum,
                                             const TriRec& r) {
-  if (a.sequential) {
-    if (r.n <= 4) {
-      const int n = r.n;
-      const double y0 = n > 0 ? load_final(y, r.e.x) : 0.0;
-      const double y1 = n > 1 ? load_final(y, r.e.y) : 0.0;
-      const double y2 = n > 2 ? load_final(y, r.e.z) : 0.0;
-      const double y3 = n > 3 ? load_final(y, r.e.w) : 0.0;
-      if (y0 != 0.0) sum -= y0 * r.v[0];
-      if (y1 != 0.0) sum -= y1 * r.v[1];
-      if (y2 != 0.0) sum -= y2 * r.v[2];
-      if (y3 != 0.0) sum -= y3 * r.v[3];
-    } else {
-      sum = subtract_sequential(a, y, sum, r.e.x, r.e.x + r.n);
-    }
-    return tri_sequential_divide(a, sum, r.d);
-  }
   if (r.n <= 4) {
     const int n = r.n;
-    const double y0 = n > 0 ? load_final(y, r.e.x) : 0.0;
-    const double y1 = n > 1 ? load_final(y, r.e.y) : 0.0;
-    const double y2 = n > 2 ? load_final(y, r.e.z) : 0.0;
-    const double y3 = n > 3 ? load_final(y, r.e.w) : 0.0;
-    if (n == 4) {
-      sum -= r.v[0] * y0 + r.v[1] * y1 + r.v[2] * y2 + r.v[3] * y3;
-    } else {
-      if (n > 0) sum -= r.v[0] * y0;
-      if (n > 1) sum -= r.v[1] * y1;
-      if (n > 2) sum -= r.v[2] * y2;
-    }
-  } else {
-    sum = subtract_overflow(a, y, sum, r.e.x, r.e.x + r.n);
+    const double y0 = n > 0 ? val(r.e.x) : 0.0;
+    const double y1 = n > 1 ? val(r.e.y) : 0.0;
+    const double y2 = n > 2 ? val(r.e.z) : 0.0;
+    const double y3 = n > 3 ? val(r.e.w) : 0.0;
+    return tri_short_output(a, sum, r, y0, y1, y2, y3);
   }
-  return a.diag != nullptr ? sum / r.d : sum;
+  for (int e = r.e.x, end = r.e.x + r.n; e < end; e += 8) {
+    double w[8], v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      w[i] = e + i < end ? a.ovf_value[e + i] : 0.0;
+      v[i] = e + i < end ? val(a.ovf_pos[e + i]) : 0.0;
+    }
+    tri_fold_window(a.sequential != 0, end - e, w, v, &sum);
+  }
+  return tri_divide(a, sum, r.d);
 }
 
 __device__ __forceinline__ void tri_compute(const TriSolveArgs& a, double* y, int k, int top,
                                             const TriRec& r) {
   if (r.row > top) return;
-  y[k] = tri_apply(a, y, y[k], r);
+  y[k] = tri_apply(a, TriFinalValues{y}, y[k], r);
 }
 
 // Zero-copy staging in and out of device-visible host memory (coalesced
@@ -202,9 +163,7 @@ __global__ __launch_bounds__(256) void tri_gather_level0_kernel(TriSolveArgs a) 
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < a.num_pos;
        k += gridDim.x * blockDim.x) {
     double v = a.x[a.pos_row[k]];
-    if (k < l0_end && a.rec_row[k] <= top) {  // padding rows: INT32_MAX
-      v = a.sequential ? tri_sequential_divide(a, v, a.diag[k]) : v / a.diag[k];
-    }
+    if (k < l0_end && a.rec_row[k] <= top) v = tri_divide(a, v, a.diag[k]);  // padding rows: INT32_MAX
     a.y[k] = v;
   }
 }
@@ -247,70 +206,6 @@ struct TriRunValues {
   }
 };
 
-// tri_apply with the values read through `val` (same terms, same order).
-template <typename Val>
-__device__ __forceinline__ double tri_apply_vals(const TriSolveArgs& a, const Val& val, double sum,
-                                                 const TriRec& r) {
-  if (a.sequential) {
-    if (r.n <= 4) {
-      const int n = r.n;
-      const double y0 = n > 0 ? val(r.e.x) : 0.0;
-      const double y1 = n > 1 ? val(r.e.y) : 0.0;
-      const double y2 = n > 2 ? val(r.e.z) : 0.0;
-      const double y3 = n > 3 ? val(r.e.w) : 0.0;
-      if (y0 != 0.0) sum -= y0 * r.v[0];
-      if (y1 != 0.0) sum -= y1 * r.v[1];
-      if (y2 != 0.0) sum -= y2 * r.v[2];
-      if (y3 != 0.0) sum -= y3 * r.v[3];
-    } else {
-      for (int e = r.e.x, end = r.e.x + r.n; e < end; ++e) {
-        const double v = val(a.ovf_pos[e]);
-        if (v != 0.0) sum -= v * a.ovf_value[e];
-      }
-    }
-    return tri_sequential_divide(a, sum, r.d);
-  }
-  if (r.n <= 4) {
-    const int n = r.n;
-    const double y0 = n > 0 ? val(r.e.x) : 0.0;
-    const double y1 = n > 1 ? val(r.e.y) : 0.0;
-    const double y2 = n > 2 ? val(r.e.z) : 0.0;
-    const double y3 = n > 3 ? val(r.e.w) : 0.0;
-    if (n == 4) {
-      sum -= r.v[0] * y0 + r.v[1] * y1 + r.v[2] * y2 + r.v[3] * y3;
-    } else {
-      if (n > 0) sum -= r.v[0] * y0;
-      if (n > 1) sum -= r.v[1] * y1;
-      if (n > 2) sum -= r.v[2] * y2;
-    }
-  } else {
-    // subtract_overflow's grouping: batches of 8 as two groups of 4, then 4s,
-    // then the 1-3 remaining one by one.
-    int e = r.e.x;
-    const int end = r.e.x + r.n;
-    for (; e + 7 < end; e += 8) {
-      double p[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) p[i] = a.ovf_value[e + i] * val(a.ovf_pos[e + i]);
-      sum -= p[0] + p[1] + p[2] + p[3];
-      sum -= p[4] + p[5] + p[6] + p[7];
-    }
-    for (; e + 3 < end; e += 4) {
-      sum -= a.ovf_value[e] * val(a.ovf_pos[e]) + a.ovf_value[e + 1] * val(a.ovf_pos[e + 1]) +
-             a.ovf_value[e + 2] * val(a.ovf_pos[e + 2]) +
-             a.ovf_value[e + 3] * val(a.ovf_pos[e + 3]);
-    }
-    if (e < end) {
-      sum -= a.ovf_value[e] * val(a.ovf_pos[e]);
-      if (e + 1 < end) {
-        sum -= a.ovf_value[e + 1] * val(a.ovf_pos[e + 1]);
-        if (e + 2 < end) sum -= a.ovf_value[e + 2] * val(a.ovf_pos[e + 2]);
-      }
-    }
-  }
-  return a.diag != nullptr ? sum / r.d : sum;
-}
-
 // Narrow levels [level_begin, level_end) on one CU, one level after the
 // other. The run's own outputs live in LDS (written there and to global
 // memory for the later launches), so a level hands its values to the next
@@ -352,7 +247,7 @@ __global__ __launch_bounds__(kTriThreads) void tri_levels_cu_kernel(TriSolveArgs
       if (k >= le) return;
       // Not computed (row above top, or padding): the input, as tri_compute
       // leaves it in y.
-      const double out = r.row > top ? y[k] : tri_apply_vals(a, val, y[k], r);
+      const double out = r.row > top ? y[k] : tri_apply(a, val, y[k], r);
       lds_y[k - seg_lo] = out;
       if (r.row <= top) y[k] = out;
     };
@@ -379,11 +274,11 @@ __global__ __launch_bounds__(kTriThreads) void tri_levels_cu_kernel(TriSolveArgs
 // workgroups, dispatched first: every wait ends. The wait, the computation
 // and the store sit in one loop body, so a lane whose reader shares its wave
 // stores before the wave spins again.
-constexpr unsigned long long kTriPending = 0x7ff0deadbeef0001ull;  // a NaN no arithmetic makes
 constexpr uint64_t kTriMaxWaitTicks = 20000000;  // 0.2 s of the 100 MHz wall clock
 
-__device__ __forceinline__ bool tri_pending(double v) {
-  return static_cast<unsigned long long>(__double_as_longlong(v)) == kTriPending;
+// Bounded wait ran out (never expected): report, the host fails loudly.
+__device__ __forceinline__ void tri_report_stall(const TriSolveArgs& a) {
+  if (a.fail != nullptr) __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // y[k] = x[row(k)], or "pending" for the outputs this solve computes; the
@@ -392,7 +287,7 @@ __device__ __forceinline__ bool tri_pending(double v) {
 __global__ __launch_bounds__(256) void tri_init_kernel(TriSolveArgs a0) {
   const TriSolveArgs a = TriRhs(a0, blockIdx.y);
   const int top = *a.top;
-  const double pending = __longlong_as_double(static_cast<long long>(kTriPending));
+  const double pending = tri_pending_mark();
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < a.num_pos;
        k += gridDim.x * blockDim.x) {
     const int row = a.pos_row[k];
@@ -401,9 +296,7 @@ __global__ __launch_bounds__(256) void tri_init_kernel(TriSolveArgs a0) {
       const int rrow = a.rec_row[k];  // INT32_MAX for padding
       v = a.x[row];
       if (rrow <= top) {
-        if (a.diag != nullptr) {
-          v = a.sequential ? tri_sequential_divide(a, v, a.diag[k]) : v / a.diag[k];
-        }
+        if (a.diag != nullptr) v = tri_divide(a, v, a.diag[k]);
         a.x[row] = v;  // the scatter, fused
       }
     } else {
@@ -424,32 +317,6 @@ __device__ __forceinline__ void tri_backoff(const TriSolveArgs& a, int* units) {
   *units = min(*units * 2, a.poll_max);
 }
 
-__device__ __forceinline__ int tri_entry_pos(const TriSolveArgs& a, const int4& e, int n, int j) {
-  if (n > 4) return a.ovf_pos[e.x + j];
-  return j == 0 ? e.x : j == 1 ? e.y : j == 2 ? e.z : e.w;
-}
-
-// tri_apply for n <= 4 with the entry values already in registers.
-__device__ __forceinline__ double tri_apply4(const TriSolveArgs& a, double sum, const TriRec& r,
-                                             double y0, double y1, double y2, double y3) {
-  const int n = r.n;
-  if (a.sequential) {
-    if (y0 != 0.0) sum -= y0 * r.v[0];
-    if (y1 != 0.0) sum -= y1 * r.v[1];
-    if (y2 != 0.0) sum -= y2 * r.v[2];
-    if (y3 != 0.0) sum -= y3 * r.v[3];
-    return tri_sequential_divide(a, sum, r.d);
-  }
-  if (n == 4) {
-    sum -= r.v[0] * y0 + r.v[1] * y1 + r.v[2] * y2 + r.v[3] * y3;
-  } else {
-    if (n > 0) sum -= r.v[0] * y0;
-    if (n > 1) sum -= r.v[1] * y1;
-    if (n > 2) sum -= r.v[2] * y2;
-  }
-  return a.diag != nullptr ? sum / r.d : sum;
-}
-
 // Output k of the sync-free solve: wait for its entries, compute, store.
 //
 // The wait loop's exit is wave-uniform (`__ballot` over the lanes still
@@ -465,7 +332,7 @@ __device__ __forceinline__ void tri_syncfree_output(const TriSolveArgs& a, int k
   const double in = done ? 0.0 : a.x[r.row];
   int backoff = 1;
   const uint64_t t0 = wall_clock64();  // 100 MHz
-  const double pend = __longlong_as_double(static_cast<long long>(kTriPending));
+  const double pend = tri_pending_mark();
   // n <= 4: one poll round loads the entries still pending at once and keeps
   // them: the values that end the wait are the ones the output is computed
   // from (a hop is one round trip, not a readiness walk plus a reload), and a
@@ -474,8 +341,8 @@ __device__ __forceinline__ void tri_syncfree_output(const TriSolveArgs& a, int k
   double y0 = n > 0 ? pend : 0.0, y1 = n > 1 ? pend : 0.0;
   double y2 = n > 2 ? pend : 0.0, y3 = n > 3 ? pend : 0.0;
   // n > 4: the output folds its entries in evaluation order as they become
-  // final (the same operations as subtract_overflow / subtract_sequential,
-  // so the same bits): by the time its last input arrives only the groups
+  // final (tri_fold_window: the same operations as tri_apply, so the same
+  // bits): by the time its last input arrives only the groups
   // after the last stall are left, and a deep chain of long outputs advances
   // by one group fold per hop instead of one whole sum. The wait bound
   // restarts on progress (a stall detector, not a budget for the chain).
@@ -493,13 +360,12 @@ __device__ __forceinline__ void tri_syncfree_output(const TriSolveArgs& a, int k
       const bool pending = tri_pending(y0) || tri_pending(y1) || tri_pending(y2) ||
                            tri_pending(y3);
       if (!pending) {
-        const double out = tri_apply4(a, in, r, y0, y1, y2, y3);
+        const double out = tri_short_output(a, in, r, y0, y1, y2, y3);
         a.x[r.row] = out;  // the scatter, fused
         __hip_atomic_store(y + k, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         done = true;
       } else if (wall_clock64() - t0 > kTriMaxWaitTicks) {
-        // Bounded wait (never expected): report and leave, the host fails loudly.
-        if (a.fail != nullptr) __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        tri_report_stall(a);
         done = true;
       } else {
         tri_backoff(a, &backoff);
@@ -508,54 +374,17 @@ __device__ __forceinline__ void tri_syncfree_output(const TriSolveArgs& a, int k
     }
     const int e0 = e;
     while (e < end) {
-      // Up to 8 values per round, their loads in flight together.
+      // Up to 8 values per round, their loads in flight together; an entry's
+      // own value is read from the overflow array when the entry is folded.
       double v[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) v[i] = e + i < end ? load_final(y, a.ovf_pos[e + i]) : 0.0;
-      int took = 0;
-      if (a.sequential) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          if (took != i || e + i >= end || tri_pending(v[i])) continue;
-          if (v[i] != 0.0) sum -= v[i] * a.ovf_value[e + i];
-          took = i + 1;
-        }
-      } else {
-#pragma unroll
-        for (int g = 0; g < 8; g += 4) {
-          if (took != g || e + g + 3 >= end) continue;
-          if (tri_pending(v[g]) || tri_pending(v[g + 1]) || tri_pending(v[g + 2]) ||
-              tri_pending(v[g + 3])) {
-            continue;
-          }
-          sum -= a.ovf_value[e + g] * v[g] + a.ovf_value[e + g + 1] * v[g + 1] +
-                 a.ovf_value[e + g + 2] * v[g + 2] + a.ovf_value[e + g + 3] * v[g + 3];
-          took = g + 4;
-        }
-        // The tail (fewer than 4 left), one subtraction per entry, all final.
-        const int left = end - e - took;
-        if (took < 8 && left > 0 && left < 4) {
-          const int t = took;
-          bool ready = true;
-#pragma unroll
-          for (int i = 0; i < 3; ++i) {
-            if (i < left && t + i < 8) ready = ready && !tri_pending(v[t + i]);
-          }
-          if (ready && t + left <= 8) {
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-              if (i < left) sum -= a.ovf_value[e + t + i] * v[t + i];
-            }
-            took = t + left;
-          }
-        }
-      }
+      const int took = tri_fold_window(a.sequential != 0, end - e, a.ovf_value + e, v, &sum);
       e += took;
       if (took < 8) break;  // a pending value, or the end
     }
     if (e == end) {
-      const double out = a.sequential ? tri_sequential_divide(a, sum, r.d)
-                                      : (a.diag != nullptr ? sum / r.d : sum);
+      const double out = tri_divide(a, sum, r.d);
       a.x[r.row] = out;  // the scatter, fused
       __hip_atomic_store(y + k, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       done = true;
@@ -563,7 +392,7 @@ __device__ __forceinline__ void tri_syncfree_output(const TriSolveArgs& a, int k
       t_progress = wall_clock64();
       backoff = 1;
     } else if (wall_clock64() - t_progress > kTriMaxWaitTicks) {
-      if (a.fail != nullptr) __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      tri_report_stall(a);
       done = true;
     } else {
       tri_backoff(a, &backoff);
@@ -619,7 +448,7 @@ __device__ __forceinline__ double tri_chain_load(const TriSolveArgs& a, const do
   if (p >= a.seg_begin && p < a.seg_end) {
     if (__hip_atomic_load(ready + (p - a.seg_begin), __ATOMIC_ACQUIRE,
                           __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
-      return __longlong_as_double(static_cast<long long>(kTriPending));
+      return tri_pending_mark();
     }
     return vals[p - a.seg_begin];
   }
@@ -715,53 +544,16 @@ __global__ __launch_bounds__(kTriThreads) void tri_chain_kernel(TriSolveArgs a0)
       double out = 0.0;
       if (r.n <= 4) {
         if (!(tri_pending(v[0]) || tri_pending(v[1]) || tri_pending(v[2]) || tri_pending(v[3]))) {
-          out = tri_apply4(a, sum, r, v[0], v[1], v[2], v[3]);
+          out = tri_short_output(a, sum, r, v[0], v[1], v[2], v[3]);
           finished = true;
         }
       } else {
-        int took = 0;
-        if (a.sequential) {
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            if (took != u || e + u >= end || tri_pending(v[u])) continue;
-            if (v[u] != 0.0) sum -= v[u] * wval[u];
-            took = u + 1;
-          }
-        } else {
-#pragma unroll
-          for (int g = 0; g < 8; g += 4) {
-            if (took != g || e + g + 3 >= end) continue;
-            if (tri_pending(v[g]) || tri_pending(v[g + 1]) || tri_pending(v[g + 2]) ||
-                tri_pending(v[g + 3])) {
-              continue;
-            }
-            sum -= wval[g] * v[g] + wval[g + 1] * v[g + 1] + wval[g + 2] * v[g + 2] +
-                   wval[g + 3] * v[g + 3];
-            took = g + 4;
-          }
-          const int left = end - e - took;
-          if (took < 8 && left > 0 && left < 4) {
-            const int t = took;
-            bool all_final = true;
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-              if (u < left && t + u < 8) all_final = all_final && !tri_pending(v[t + u]);
-            }
-            if (all_final && t + left <= 8) {
-#pragma unroll
-              for (int u = 0; u < 3; ++u) {
-                if (u < left) sum -= wval[t + u] * v[t + u];
-              }
-              took = t + left;
-            }
-          }
-        }
+        const int took = tri_fold_window(a.sequential != 0, end - e, wval, v, &sum);
         if (took > 0) {
           e += took;
           progress = true;
           if (e == end) {
-            out = a.sequential ? tri_sequential_divide(a, sum, r.d)
-                               : (a.diag != nullptr ? sum / r.d : sum);
+            out = tri_divide(a, sum, r.d);
             finished = true;
           } else {
 #pragma unroll
@@ -792,7 +584,7 @@ __global__ __launch_bounds__(kTriThreads) void tri_chain_kernel(TriSolveArgs a0)
         const uint64_t now = wall_clock64();
         if (polls == 64) t_progress = now;  // first stalled check of this wait
         if (now - t_progress > kTriMaxWaitTicks) {
-          if (a.fail != nullptr) __hip_atomic_store(a.fail, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          tri_report_stall(a);
           failed = true;
           break;
         }
@@ -814,20 +606,39 @@ __global__ __launch_bounds__(kTriThreads) void tri_chain_kernel(TriSolveArgs a0)
 
 namespace milp_launch {
 
+namespace {
+
+// Grids of the kernels that walk the rows [first_col, num_rows) and the
+// positions (grid-stride loops).
+struct TriGrid {
+  int row_blocks, pos_blocks;
+  explicit TriGrid(const milp_kernels::TriSolveArgs& a)
+      : row_blocks(std::max(1, std::min(1024, (a.num_rows - a.first_col + 255) / 256))),
+        pos_blocks(std::max(1, std::min(1024, (a.num_pos + 255) / 256))) {}
+};
+
+// Zero-copy staging around a plan; nothing to do when the caller copies.
+hipError_t tri_stage_in(const milp_kernels::TriSolveArgs& args, int num_rhs, hipStream_t s) {
+  if (args.host_x == nullptr) return hipSuccess;
+  milp_kernels::tri_copy_in_kernel<<<dim3(TriGrid(args).row_blocks, num_rhs), 256, 0, s>>>(args);
+  return hipGetLastError();
+}
+
+hipError_t tri_stage_out(const milp_kernels::TriSolveArgs& args, int num_rhs, hipStream_t s) {
+  if (args.host_x == nullptr) return hipSuccess;
+  milp_kernels::tri_copy_out_kernel<<<dim3(TriGrid(args).row_blocks, num_rhs), 256, 0, s>>>(args);
+  return hipGetLastError();
+}
+
+}  // namespace
+
 hipError_t tri_transpose_lower_syncfree(const milp_kernels::TriSolveArgs& args,
                                         const int* segs, int num_segs, hipStream_t s,
                                         int num_rhs) {
   if (args.num_work <= 0) return hipSuccess;
-  const int row_blocks =
-      std::max(1, std::min(1024, (args.num_rows - args.first_col + 255) / 256));
-  hipError_t e;
-  if (args.host_x != nullptr) {
-    milp_kernels::tri_copy_in_kernel<<<dim3(row_blocks, num_rhs), 256, 0, s>>>(args);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  const int pos_blocks = std::max(1, std::min(1024, (args.num_pos + 255) / 256));
-  milp_kernels::tri_init_kernel<<<dim3(pos_blocks, num_rhs), 256, 0, s>>>(args);
+  hipError_t e = tri_stage_in(args, num_rhs, s);
+  if (e != hipSuccess) return e;
+  milp_kernels::tri_init_kernel<<<dim3(TriGrid(args).pos_blocks, num_rhs), 256, 0, s>>>(args);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   milp_kernels::TriSolveArgs a = args;
@@ -847,46 +658,30 @@ hipError_t tri_transpose_lower_syncfree(const milp_kernels::TriSolveArgs& args,
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  if (args.host_x == nullptr) return hipSuccess;
-  milp_kernels::tri_copy_out_kernel<<<dim3(row_blocks, num_rhs), 256, 0, s>>>(args);
-  return hipGetLastError();
+  return tri_stage_out(args, num_rhs, s);
 }
 
 hipError_t tri_transpose_lower_persistent(const milp_kernels::TriSolveArgs& args, int groups,
                                           int xcd_stride, hipStream_t s) {
   if (args.num_work <= 0) return hipSuccess;
-  const int row_blocks =
-      std::max(1, std::min(1024, (args.num_rows - args.first_col + 255) / 256));
-  hipError_t e;
-  if (args.host_x != nullptr) {
-    milp_kernels::tri_copy_in_kernel<<<row_blocks, 256, 0, s>>>(args);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  const int pos_blocks = std::max(1, std::min(1024, (args.num_pos + 255) / 256));
-  milp_kernels::tri_init_kernel<<<pos_blocks, 256, 0, s>>>(args);
+  hipError_t e = tri_stage_in(args, 1, s);
+  if (e != hipSuccess) return e;
+  milp_kernels::tri_init_kernel<<<TriGrid(args).pos_blocks, 256, 0, s>>>(args);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   milp_kernels::tri_syncfree_persistent_kernel<<<groups * xcd_stride, milp_kernels::kTriThreads,
                                                  0, s>>>(args, xcd_stride);
   e = hipGetLastError();
-  if (e != hipSuccess || args.host_x == nullptr) return e;
-  milp_kernels::tri_copy_out_kernel<<<row_blocks, 256, 0, s>>>(args);
-  return hipGetLastError();
+  if (e != hipSuccess) return e;
+  return tri_stage_out(args, 1, s);
 }
 
 hipError_t tri_transpose_lower(const milp_kernels::TriSolveArgs& args, const int* segments,
                                int num_segments, hipStream_t s) {
   if (args.num_work <= 0) return hipSuccess;
-  const int row_blocks =
-      std::max(1, std::min(1024, (args.num_rows - args.first_col + 255) / 256));
-  hipError_t e;
-  if (args.host_x != nullptr) {
-    milp_kernels::tri_copy_in_kernel<<<row_blocks, 256, 0, s>>>(args);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  const int pos_blocks = std::min(1024, (args.num_pos + 255) / 256);
+  hipError_t e = tri_stage_in(args, 1, s);
+  if (e != hipSuccess) return e;
+  const int pos_blocks = TriGrid(args).pos_blocks;
   // Level 0 alone over the chip (the first segment is (-1, blocks)) and a
   // diagonal to divide by: fused into the gather.
   const bool fuse0 = args.fuse_level0 && args.diag != nullptr && num_segments > 0 &&
@@ -915,11 +710,9 @@ hipError_t tri_transpose_lower(const milp_kernels::TriSolveArgs& args, const int
   // measured 80 us against 5 + 15 us for this scatter plus the coalesced
   // copy-out: scattered 8-byte PCIe writes.)
   milp_kernels::tri_scatter_kernel<<<work_blocks, 256, 0, s>>>(args);
-  if (args.host_x == nullptr) return hipGetLastError();
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  milp_kernels::tri_copy_out_kernel<<<row_blocks, 256, 0, s>>>(args);
-  return hipGetLastError();
+  return tri_stage_out(args, 1, s);
 }
 
 }  // namespace milp_launch

@@ -62,11 +62,15 @@ VARIANTS = {
 
 
 # The default single-launch kernel on every case; the level-plan variants on
-# two (their kernels are shared, only the schedule walk differs).
+# two (their kernels are shared, only the schedule walk differs); the deep
+# chain of long outputs on the plans that evaluate a long output their own
+# way (whole from final values, or folded from LDS).
 _PARAMS = [(c, "syncfree") for c in _cases()] + [
     (c, v) for c in _cases() if c[0] in ("c5_71", "dense_dual")
     for v in ("levels", "levels_copies", "syncfree_copies", "persistent_xcd",
-              "persistent_chip", "chain", "wide_chain", "padded", "no_pair_btran")]
+              "persistent_chip", "chain", "wide_chain", "padded", "no_pair_btran")] + [
+    (c, v) for c in _cases() if c[0] == "dense_deep"
+    for v in ("levels", "chain", "wide_chain", "persistent_chip")]
 
 
 @pytest.mark.parametrize("case,variant", _PARAMS, ids=lambda x: x if isinstance(x, str) else x[0])
