@@ -258,6 +258,37 @@ int mi_lp_compute_dictionary(mi_lp* h, const double* column_scales, int32_t scal
                              int64_t* nnz);
 int mi_lp_get_dictionary(const mi_lp* h, int64_t* row_starts, int32_t* cols, double* values);
 
+/* Several rows of rho^T [A | I] in one call that reads A once per panel of up
+ * to 16 vectors (what a cut loop otherwise computes on the host, one row at a
+ * time, after sat/linear_programming_constraint.cc:1247). No Glop call does
+ * this; each result is defined by two pieces of Glop's public surface:
+ *   mi_lp_row_combinations               out[j (n+m) + col] = dot(col, y_j) for j < k
+ *                                        and EVERY column col of [A | I], where dot is
+ *                                        CompactSparseMatrix::ColumnScalarProduct
+ *                                        (sparse.h:514-542): four accumulators over the
+ *                                        column's entries in groups of four from +0.0,
+ *                                        ((r1 + r2) + r3) + r4, then the <= 3 tail terms
+ *                                        in order, every product and sum rounded
+ *                                        separately. An empty column gives +0.0, a slack
+ *                                        column 0.0 + y[r]. The full row over all n+m
+ *                                        columns, unfiltered: no relevant mask, no drop
+ *                                        tolerance, no cost term. Changes no state a
+ *                                        later solve reads.
+ *   mi_lp_get_tableau_rows               the same with y_j = the values of
+ *                                        GetUnitRowLeftInverse(rows[j])
+ *                                        (revised_simplex.h:209) of the current basis,
+ *                                        computed by k host left solves in the caller's
+ *                                        order; left_inverses (k x m, may be NULL)
+ *                                        receives them. Side effects: exactly those of k
+ *                                        mi_lp_get_unit_row_left_inverse calls.
+ * y: k x m, out: k x (n+m), both vector-major. k = 0 writes nothing and
+ * succeeds; k < 0 or a row outside [0, m) is MI_LP_ERROR_INVALID_PROBLEM with
+ * nothing written; other errors as mi_lp_get_unit_row_left_inverse. */
+int mi_lp_row_combinations(mi_lp* h, const double* y, int32_t k, double* out);
+/* rows: k basic row indices. out: k x (n+m). left_inverses: k x m, or NULL. */
+int mi_lp_get_tableau_rows(mi_lp* h, const int32_t* rows, int32_t k, double* out,
+                           double* left_inverses);
+
 /* interrupt may be NULL; a non-zero value stops the solve like a time limit
  * (glop_interface.cc:138-140). */
 int mi_lp_solve(mi_lp* h, const volatile int32_t* interrupt, mi_lp_result* out);

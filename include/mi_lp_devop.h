@@ -52,6 +52,15 @@ typedef struct mi_devop_paths {
   int32_t list_mapped;     /* the last list also went to the mapped host mirrors */
 } mi_devop_paths;
 
+/* DeviceLp::LastPanel: which kernels the last column_dots_panel went through. */
+enum { MI_DEVOP_PANEL_NONE = 0, MI_DEVOP_PANEL_SHORT_COLUMNS = 1, MI_DEVOP_PANEL_LONG_COLUMNS = 2 };
+typedef struct mi_devop_panel {
+  int32_t sparse; /* MI_DEVOP_PANEL_* of the CSC kernel */
+  int32_t dense;  /* the dense-block kernel ran */
+  int32_t panels; /* panels of up to 16 vectors */
+  int32_t width;  /* padded width of the last panel: 1, 4 or 16 */
+} mi_devop_panel;
+
 typedef struct mi_devop_api {
   /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
   mi_devop* (*create)(int device, int m, int n, const int64_t* col_starts,
@@ -84,6 +93,14 @@ typedef struct mi_devop_api {
                                    double leaving_value, int entering_col);
   int (*dual_download_reduced_costs)(mi_devop* h, double* rc);
   int (*last_paths)(mi_devop* h, mi_devop_paths* out);
+  /* Appended after last_paths: the entries above keep their places.
+   * y: k x m, out: k x N, both vector-major (DeviceLp::ColumnDotsPanel). */
+  int (*column_dots_panel)(mi_devop* h, const double* y, int k, double* out);
+  int (*last_panel)(mi_devop* h, mi_devop_panel* out);
+  /* Measurement only: device-event milliseconds of the panel kernels and of
+   * the list_dots kernels since the previous call (the first call turns the
+   * event timing on and returns zeros). */
+  int (*take_kernel_ms)(mi_devop* h, double* panel_ms, double* list_dots_ms);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

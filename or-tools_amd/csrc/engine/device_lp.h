@@ -126,6 +126,35 @@ class DeviceLp : public DeviceSolver {
   // Changes whenever the device-side update-row list (and its flags) changes.
   uint64_t list_epoch() const;
 
+  // --- column dots of k vectors in one pass (kernels/panel_kernels.hip) ----
+  // out[j * N + col] = a_col . y_j (ColumnScalarProduct's order, sparse.h:
+  // 514-542) for j < k and every column of [A | I]: no mask, no drop
+  // tolerance. y is k x m and out k x N, both vector-major on the host. The
+  // vectors go to the device row-interleaved in panels of up to 16 (widths 1,
+  // 4 and 16, padded with zero vectors whose results are not stored), and A
+  // is read once per panel. Synchronizes before it returns.
+  // The panel's device buffers (interleaved vectors, interleaved and
+  // vector-major results: 8 m W + 8 N W + 8 N min(k, 16) bytes at width W)
+  // are its own, allocated at first use, grown as needed and freed with the
+  // handle; at config 5's size (N = 1.1 M) one 16-vector output panel is
+  // 141 MB. Nothing a solve reads is written: not the update row, its list or
+  // flags, the masks, the dual-mode arrays or last_paths(). Not counted in
+  // mi_lp_kernel_stats (its ids are taken).
+  void ColumnDotsPanel(const double* y, int k, double* out);
+  // Which kernels the last ColumnDotsPanel went through (test record).
+  enum PanelSparse { kPanelNone = 0, kPanelShortColumns = 1, kPanelLongColumns = 2 };
+  struct LastPanel {
+    int sparse = kPanelNone;  // shape of the CSC kernel; none: no column went through it
+    bool dense = false;       // the dense-block kernel ran
+    int panels = 0;
+    int width = 0;            // of the last panel
+  };
+  LastPanel last_panel() const { return last_panel_; }
+  // Device-event time of the panel kernels (transfers excluded) since the
+  // last call, for the measurement script; events are recorded from the
+  // first call on.
+  double TakePanelKernelMs();
+
   // --- 1 + ||a_j||^2 for relevant j (identity basis) -------------------
   void ColumnSquaredNorms(std::vector<double>* out);
 
@@ -360,8 +389,22 @@ class DeviceLp : public DeviceSolver {
                                      int entering_col);
   void ShardedDualBoxedFlips(const std::vector<int>* cols, double threshold,
                              std::vector<uint8_t>* flags);
+  void ShardedColumnDotsPanel(const double* y, int k, double* out);
   void ShardedStats();
   void FlushOwnMasks();
+  // ColumnDotsPanel's own buffers (not in allocations_: they outlive a
+  // matrix upload and are sized by capacity).
+  void PanelReserve(int width, int kp);
+  void FreePanelBuffers();
+  double* d_panel_y_ = nullptr;    // interleaved vectors, m x width
+  double* h_panel_y_ = nullptr;    // pinned staging of it
+  double* d_panel_i_ = nullptr;    // interleaved results, N x width
+  double* d_panel_out_ = nullptr;  // vector-major results, kp x N
+  size_t panel_y_cap_ = 0, panel_i_cap_ = 0, panel_out_cap_ = 0;  // doubles
+  LastPanel last_panel_;
+  bool panel_timing_ = false;
+  double panel_kernel_ms_ = 0.0;
+  void* ev_panel_[2] = {nullptr, nullptr};
   bool is_shard_ = false;
   std::vector<std::unique_ptr<DeviceLp>> shards_;  // null: a block owned by another process
   ExchangeFn exchange_fn_ = nullptr;

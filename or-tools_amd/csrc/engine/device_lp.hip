@@ -68,6 +68,7 @@ DeviceLp::~DeviceLp() {
   if (stream_ != nullptr) (void)hipStreamSynchronize(S(stream_));
   SdualFree();
   FreeTriBuffers();
+  FreePanelBuffers();
   for (void* p : allocations_) (void)hipFree(p);
   if (h_pin_i_) (void)hipHostFree(h_pin_i_);
   if (h_pin_d_) (void)hipHostFree(h_pin_d_);
@@ -1639,6 +1640,127 @@ void DeviceLp::Pricing(const std::vector<double>& c, const std::vector<double>& 
   Download(h_pin_d_, d_out_n_, n_total_ * sizeof(double));
   CopyHost(rc->data(), h_pin_d_, n_total_ * sizeof(double));
   if (fused && n_list > 0) CopyHost(list_dots->data(), h_pin_d2_, n_list * sizeof(double));
+}
+
+void DeviceLp::FreePanelBuffers() {
+  if (d_panel_y_) (void)hipFree(d_panel_y_);
+  if (d_panel_i_) (void)hipFree(d_panel_i_);
+  if (d_panel_out_) (void)hipFree(d_panel_out_);
+  if (h_panel_y_) (void)hipHostFree(h_panel_y_);
+  d_panel_y_ = d_panel_i_ = d_panel_out_ = h_panel_y_ = nullptr;
+  panel_y_cap_ = panel_i_cap_ = panel_out_cap_ = 0;
+  for (void*& e : ev_panel_) {
+    if (e) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(e));
+    e = nullptr;
+  }
+}
+
+// Grows the panel buffers to one panel of `width` holding `kp` vectors. The
+// stream is idle between panels (each ends with a synchronizing download).
+void DeviceLp::PanelReserve(int width, int kp) {
+  const auto grow = [this](double** p, size_t* cap, size_t n, const char* what) {
+    if (n <= *cap) return;
+    if (*p) Check(hipFree(*p), what);
+    *p = nullptr;
+    *cap = 0;
+    Check(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(double)), what);
+    *cap = n;
+  };
+  const size_t ym = std::max<size_t>(1, size_t(m_) * width);
+  if (ym > panel_y_cap_) {
+    if (h_panel_y_) Check(hipHostFree(h_panel_y_), "panel staging");
+    h_panel_y_ = nullptr;
+    Check(hipHostMalloc(reinterpret_cast<void**>(&h_panel_y_), ym * sizeof(double)),
+          "panel staging");
+  }
+  grow(&d_panel_y_, &panel_y_cap_, ym, "panel vectors");
+  grow(&d_panel_i_, &panel_i_cap_, size_t(n_total_) * width, "panel results");
+  grow(&d_panel_out_, &panel_out_cap_, size_t(n_total_) * kp, "panel output");
+}
+
+double DeviceLp::TakePanelKernelMs() {
+  double ms = panel_kernel_ms_;
+  panel_kernel_ms_ = 0.0;
+  panel_timing_ = true;
+  for (auto& d : shards_) {
+    if (d) ms += d->TakePanelKernelMs();
+  }
+  return ms;
+}
+
+void DeviceLp::ColumnDotsPanel(const double* y, int k, double* out) {
+  if (!shards_.empty()) return ShardedColumnDotsPanel(y, k, out);
+  last_panel_ = LastPanel();
+  if (k <= 0 || n_total_ <= 0) return;
+  DeviceOp("column dots panel");
+  const double sparse_avg =
+      (nd_ > 0 ? (ns_ > 0 ? double(sparse_entries_) / ns_ : 0.0) : avg_col_len_);
+  const bool long_columns = sparse_avg >= 32.0;  // LaunchColumnDots' rule
+  const int sparse_cols = nd_ > 0 ? ns_ : n_total_;
+  if (panel_timing_ && ev_panel_[0] == nullptr) {
+    for (void*& e : ev_panel_) {
+      hipEvent_t ev;
+      Check(hipEventCreate(&ev), "hipEventCreate");
+      e = ev;
+    }
+  }
+  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
+    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
+    const int width = kp == 1 ? 1 : (kp <= 4 ? 4 : 16);
+    PanelReserve(width, kp);
+    for (int r = 0; r < m_; ++r) {
+      double* dst = h_panel_y_ + size_t(r) * width;
+      for (int v = 0; v < kp; ++v) dst[v] = y[size_t(first + v) * m_ + r];
+      for (int v = kp; v < width; ++v) dst[v] = 0.0;
+    }
+    Upload(d_panel_y_, h_panel_y_, size_t(m_) * width * sizeof(double));
+    if (panel_timing_) {
+      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
+    }
+    milp_kernels::PanelDotArgs a{};
+    a.starts = d_starts_;
+    a.rows = d_rows_;
+    a.vals = d_vals_;
+    a.y = d_panel_y_;
+    a.ncols = sparse_cols;
+    a.col_list = nd_ > 0 ? d_sparse_cols_ : nullptr;
+    a.kp = kp;
+    a.out = d_panel_i_;
+    Check(milp_launch::column_dot_panel(width, long_columns, a, S(stream_)), "column dots panel");
+    if (nd_ > 0) {
+      milp_kernels::PanelDenseArgs d{};
+      d.body = d_dense_body_;
+      d.tail = d_dense_tail_;
+      d.dense_cols = d_dense_cols_;
+      d.nd = nd_;
+      d.m = m_;
+      d.y = d_panel_y_;
+      d.kp = kp;
+      d.out = d_panel_i_;
+      Check(milp_launch::dense_dot_panel(width, d, S(stream_)), "dense dots panel");
+    }
+    Check(milp_launch::panel_deinterleave(width, d_panel_i_, n_total_, kp, d_panel_out_,
+                                          n_total_, S(stream_)),
+          "panel de-interleave");
+    if (panel_timing_) {
+      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[1]), S(stream_)), "ev");
+    }
+    Download(out + size_t(first) * n_total_, d_panel_out_,
+             size_t(kp) * n_total_ * sizeof(double));
+    if (panel_timing_) {
+      float ms = 0.0f;
+      Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(ev_panel_[0]),
+                                reinterpret_cast<hipEvent_t>(ev_panel_[1])),
+            "ev time");
+      panel_kernel_ms_ += ms;
+    }
+    last_panel_.sparse = sparse_cols > 0 ? (long_columns ? kPanelLongColumns : kPanelShortColumns)
+                                         : kPanelNone;
+    last_panel_.dense = nd_ > 0;
+    last_panel_.panels += 1;
+    last_panel_.width = width;
+  }
+  DeviceOp("column dots panel done");
 }
 
 void DeviceLp::ColumnSquaredNorms(std::vector<double>* out) {

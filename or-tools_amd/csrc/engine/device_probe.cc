@@ -217,6 +217,31 @@ int LastPaths(mi_devop* h, mi_devop_paths* out) {
   });
 }
 
+int ColumnDotsPanel(mi_devop* h, const double* y, int k, double* out) {
+  return Guard(h, [&] { h->dev.ColumnDotsPanel(y, k, out); });
+}
+
+int LastPanel(mi_devop* h, mi_devop_panel* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastPanel p = h->dev.last_panel();
+    out->sparse = p.sparse;
+    out->dense = p.dense ? 1 : 0;
+    out->panels = p.panels;
+    out->width = p.width;
+  });
+}
+
+int TakeKernelMs(mi_devop* h, double* panel_ms, double* list_dots_ms) {
+  return Guard(h, [&] {
+    *panel_ms = h->dev.TakePanelKernelMs();
+    *list_dots_ms = h->dev.stats().device_ms[MI_K_PRIMAL_NORMS];
+    h->dev.ResetStats();
+    h->dev.SetTiming(true, 1u << MI_K_PRIMAL_NORMS);
+  });
+}
+
+static_assert(int{MI_DEVOP_PANEL_LONG_COLUMNS} == int{milp::DeviceLp::kPanelLongColumns},
+              "mi_lp_devop.h restates DeviceLp's panel shapes");
 static_assert(int{MI_DEVOP_ROW_COLUMN_WISE_GENERAL} == int{milp::DeviceLp::kRowColumnWiseGeneral} &&
                   int{MI_DEVOP_ROW_LIST} == int{milp::DeviceLp::kRowList} &&
                   int{MI_DEVOP_COMPACT_CHIP_WIDE} == int{milp::DeviceLp::kCompactChipWide} &&
@@ -236,4 +261,6 @@ extern "C" const mi_devop_api mi_devop_table = {
     DualSetColBits,   DualRatioCandidates,
     DualUpdateReducedCosts, DualDownloadReducedCosts,
     LastPaths,
+    ColumnDotsPanel,  LastPanel,
+    TakeKernelMs,
 };

@@ -411,6 +411,45 @@ void DeviceLp::ShardedPricing(const std::vector<double>& c, const std::vector<do
   }
 }
 
+// Each block's k x N_s panel result, joined in block order into the k x N
+// rows (as ShardedPricing joins its reduced costs). Across processes the
+// parts travel through ExchangeParts like every other join.
+void DeviceLp::ShardedColumnDotsPanel(const double* y, int k, double* out) {
+  DeviceGuard guard{device_};
+  last_panel_ = LastPanel();
+  if (k <= 0) return;
+  const int ns = num_shards();
+  std::vector<std::string> parts(ns);
+  std::vector<double> part;
+  for (int s = 0; s < ns; ++s) {
+    if (!IsLocalShard(s)) continue;
+    DeviceLp& d = Shard(s);
+    part.assign(size_t(k) * d.n_total_, 0.0);
+    if (d.n_total_ > 0) {
+      d.ColumnDotsPanel(y, k, part.data());
+      const LastPanel p = d.last_panel();
+      last_panel_.sparse = std::max(last_panel_.sparse, p.sparse);
+      last_panel_.dense = last_panel_.dense || p.dense;
+      last_panel_.panels = p.panels;
+      last_panel_.width = p.width;
+    }
+    PartWriter w;
+    w.Put(part);
+    parts[s] = std::move(w.b);
+  }
+  ExchangeParts(&parts);
+  for (int s = 0; s < ns; ++s) {
+    PartReader r{parts[s]};
+    r.Get(&part);
+    const size_t width = size_t(shard_begin_[s + 1] - shard_begin_[s]);
+    if (part.size() != width * size_t(k)) throw DeviceError("column split: bad panel part");
+    for (int j = 0; j < k; ++j) {
+      std::copy(part.begin() + j * width, part.begin() + (j + 1) * width,
+                out + size_t(j) * n_total_ + shard_begin_[s]);
+    }
+  }
+}
+
 void DeviceLp::ShardedDualBegin(const std::vector<double>& rc,
                                 const std::vector<uint8_t>& colbits,
                                 const std::vector<double>& bound_diff) {

@@ -6226,6 +6226,59 @@ int mi_lp_get_unit_row_left_inverse(mi_lp* h, int32_t row, double* values, int32
   return MI_LP_OK;
 }
 
+int mi_lp_row_combinations(mi_lp* h, const double* y, int32_t k, double* out) {
+  if (h == nullptr || y == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  try {
+    (void)hipSetDevice(h->device);
+    h->simplex.device().ColumnDotsPanel(y, k, out);
+  } catch (const milp::DeviceError& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+  return MI_LP_OK;
+}
+
+int mi_lp_get_tableau_rows(mi_lp* h, const int32_t* rows, int32_t k, double* out,
+                           double* left_inverses) {
+  if (h == nullptr || rows == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  const int m = h->lp.m;
+  for (int32_t j = 0; j < k; ++j) {
+    if (rows[j] < 0 || rows[j] >= m) return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  if (k == 0) return MI_LP_OK;
+  try {
+    (void)hipSetDevice(h->device);
+    // The k left solves stay on the host, one GetUnitRowLeftInverse each, in
+    // the caller's order; only the products with [A | I] are batched.
+    std::vector<double> local;
+    double* y = left_inverses;
+    if (y == nullptr) {
+      local.resize(size_t(k) * m);
+      y = local.data();
+    }
+    for (int32_t j = 0; j < k; ++j) {
+      const milp::ScatteredVector& v = h->simplex.GetUnitRowLeftInverse(rows[j]);
+      for (int r = 0; r < m; ++r) y[size_t(j) * m + r] = v.values[r];
+    }
+    h->simplex.device().ColumnDotsPanel(y, k, out);
+  } catch (const milp::DeviceError& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+  return MI_LP_OK;
+}
+
 int mi_lp_compute_dictionary(mi_lp* h, const double* column_scales, int32_t scales_len,
                              int64_t* nnz) {
   if (h == nullptr || nnz == nullptr || (column_scales == nullptr && scales_len > 0)) {

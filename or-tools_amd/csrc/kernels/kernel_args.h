@@ -50,6 +50,31 @@ struct DenseArgs {
   double* out2;
 };
 
+// Column dots against a panel of K vectors (panel_kernels.hip). The vectors
+// are row-interleaved, y[r * K + v], zero for the padding vectors v >= kp;
+// the results are column-interleaved, out[col * K + v], written for v < kp.
+constexpr int kPanelMaxWidth = 16;  // the widths are 1, 4 and 16
+struct PanelDotArgs {
+  const int64_t* starts;  // CSC of [A | I]
+  const int32_t* rows;
+  const double* vals;
+  const double* y;
+  int ncols;                // columns to visit (N, or list length)
+  const int32_t* col_list;  // the columns, or nullptr for 0 .. ncols - 1
+  int kp;                   // vectors in use (<= K)
+  double* out;
+};
+struct PanelDenseArgs {  // the dense block of DenseArgs
+  const double* body;
+  const double* tail;
+  const int32_t* dense_cols;
+  int nd;
+  int m;
+  const double* y;
+  int kp;
+  double* out;
+};
+
 // Where an update-row kernel that emits the list itself puts it: the
 // ascending listed columns, their coefficients and the count, on the device
 // and (optional, null when off) mirrored into mapped host memory.
@@ -418,6 +443,15 @@ hipError_t column_dot(int mode, bool wave_per_col, const milp_kernels::DotArgs& 
                       hipStream_t s);
 // unroll: 16-byte loads in flight per lane (8, 16 or 32).
 hipError_t dense_dot(int mode, int unroll, const milp_kernels::DenseArgs& args, hipStream_t s);
+// The same dots for a panel of `width` (1, 4 or 16) vectors in one pass over
+// the columns (panel_kernels.hip). long_columns: one wave per column (the
+// wave_per_col shape of column_dot), else 4 * width lanes per column.
+hipError_t column_dot_panel(int width, bool long_columns, const milp_kernels::PanelDotArgs& args,
+                            hipStream_t s);
+hipError_t dense_dot_panel(int width, const milp_kernels::PanelDenseArgs& args, hipStream_t s);
+// out[v * ld + col] = in[col * width + v] for v < kp, col < ncols.
+hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, double* out,
+                              int64_t ld, hipStream_t s);
 hipError_t dense_pack(const int64_t* starts, const double* vals, const int32_t* dense_cols,
                       int nd, int m, double* body, double* tail, hipStream_t s);
 hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hipStream_t s);

@@ -1,0 +1,265 @@
+// Column dots of [A | I] against a panel of K vectors in one pass over A
+// (tableau rows and row combinations, include/mi_lp.h mi_lp_row_combinations).
+//
+// Every result is CompactSparseMatrix::ColumnScalarProduct (lp_data/sparse.h:
+// 514-542) of one column and one vector: four strided accumulators r1..r4
+// from +0.0, ((r1 + r2) + r3) + r4, then the <= 3 tail terms in order, every
+// product and sum rounded separately (-ffp-contract=off). These kernels
+// restate column_dot_kernel / dense_dot_kernel (simplex_kernels.hip) for K
+// vectors; the order of the terms of one (column, vector) pair is theirs.
+//
+// The vectors are row-interleaved, Y[r * K + v], so the K values a matrix
+// entry meets are contiguous. Results go to out[col * K + v] (a column's K
+// results contiguous); deinterleave_kernel turns that into the caller's
+// vector-major rows. Only vectors v < kp are stored (the others are padding).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kernel_args.h"
+
+namespace milp_kernels {
+
+namespace {
+constexpr int kWave = 64;
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+constexpr int kDenseColsPerBlock = 64;
+}  // namespace
+
+// ---------------------------------------------------------------------------
+// Short columns: lane = slot * 4K + v * 4 + c owns vector v and chain c of its
+// column and walks the chain sequentially, as quad_column_dot does (K = 1 is
+// that function). A wave holds 64 / 4K columns: one at K = 16, four at K = 4.
+// A step of a column reads 4 matrix entries (each by K lanes: a broadcast)
+// and 4 x K contiguous doubles of Y.
+template <int K>
+__global__ __launch_bounds__(256) void column_dot_panel_short_kernel(PanelDotArgs a) {
+  constexpr int kLanesPerCol = 4 * K;
+  const int lane = threadIdx.x & 63;
+  const int sub = threadIdx.x % kLanesPerCol;
+  const int v = sub >> 2;
+  const int c = sub & 3;
+  const int col_slot = blockIdx.x * (256 / kLanesPerCol) + threadIdx.x / kLanesPerCol;
+  // The lanes of a column stay converged through the shuffles: out-of-range
+  // slots walk an empty range and skip the store.
+  const bool in_range = col_slot < a.ncols;
+  const int slot = in_range ? col_slot : 0;
+  const int col = a.col_list != nullptr ? a.col_list[slot] : slot;
+  const int64_t s = a.starts[col];
+  const int64_t e = in_range ? a.starts[col + 1] : s;
+  const int64_t len = e - s;
+  const int64_t full = (len >= 4) ? (len / 4) * 4 : 0;
+  const double* __restrict__ y = a.y + v;
+  double acc = 0.0;
+  for (int64_t i = s + c; i < s + full; i += 4) {
+    acc += a.vals[i] * y[static_cast<int64_t>(a.rows[i]) * K];
+  }
+  const int g = lane & ~3;
+  const double r1 = __shfl(acc, g + 0, kWave);
+  const double r2 = __shfl(acc, g + 1, kWave);
+  const double r3 = __shfl(acc, g + 2, kWave);
+  const double r4 = __shfl(acc, g + 3, kWave);
+  double result = r1 + r2 + r3 + r4;
+  for (int64_t i = s + full; i < e; ++i) {
+    result += a.vals[i] * y[static_cast<int64_t>(a.rows[i]) * K];
+  }
+  if (c == 0 && in_range && v < a.kp) a.out[static_cast<int64_t>(col) * K + v] = result;
+}
+
+// ---------------------------------------------------------------------------
+// Long columns: one wave (one workgroup) per column, wave_column_dot's
+// structure with K products per lane. The 64 lanes load 64 consecutive
+// entries (coalesced) and the K contiguous Y values of their rows; the 64 x K
+// products go through LDS (prod[v][entry], rows padded against bank
+// conflicts), and lane v * 4 + c folds chain c of vector v in entry order.
+constexpr int kPanelProdStride = 68;
+
+template <int K>
+__global__ __launch_bounds__(64) void column_dot_panel_long_kernel(PanelDotArgs a) {
+  __shared__ double prod[K * kPanelProdStride];
+  const int lane = threadIdx.x;
+  const int v = (lane >> 2) % K;  // lanes >= 4K repeat a vector and never store
+  const int c = lane & 3;
+  const int slot = blockIdx.x;  // < ncols: the grid is exactly ncols workgroups
+  const int col = a.col_list != nullptr ? a.col_list[slot] : slot;
+  const int64_t s = a.starts[col];
+  const int64_t e = a.starts[col + 1];
+  const int64_t len = e - s;
+  const int64_t full = (len >= 4) ? (len / 4) * 4 : 0;
+  double acc = 0.0;
+  for (int64_t base = 0; base < full; base += kWave) {
+    const int64_t idx = base + lane;
+    if (idx < full) {
+      const double x = a.vals[s + idx];
+      const double* __restrict__ yr = a.y + static_cast<int64_t>(a.rows[s + idx]) * K;
+#pragma unroll
+      for (int u = 0; u < K; ++u) prod[u * kPanelProdStride + lane] = x * yr[u];
+    }
+    __syncthreads();
+    const int64_t nvalid = (full - base) < kWave ? (full - base) : kWave;
+    const int nt = static_cast<int>(nvalid >> 2);  // terms of each chain in this chunk
+    for (int t = 0; t < nt; ++t) acc += prod[v * kPanelProdStride + (t << 2) + c];
+    __syncthreads();
+  }
+  const int g = lane & ~3;
+  const double r1 = __shfl(acc, g + 0, kWave);
+  const double r2 = __shfl(acc, g + 1, kWave);
+  const double r3 = __shfl(acc, g + 2, kWave);
+  const double r4 = __shfl(acc, g + 3, kWave);
+  double result = r1 + r2 + r3 + r4;
+  for (int64_t i = s + full; i < e; ++i) {
+    result += a.vals[i] * a.y[static_cast<int64_t>(a.rows[i]) * K + v];
+  }
+  if (c == 0 && lane < 4 * K && v < a.kp) a.out[static_cast<int64_t>(col) * K + v] = result;
+}
+
+// ---------------------------------------------------------------------------
+// Dense block (layout in kernel_args.h DenseArgs): dense_dot_kernel with K
+// accumulators per lane. A workgroup owns 64 dense columns, wave k streams
+// chain k of them with contiguous 1-KiB steps. The chain index is
+// wave-uniform and the K y-values of a row are contiguous, so they come from
+// scalar loads. The 4 x K partial sums of a column meet in LDS; wave k then
+// folds vectors k, k + 4, ...: ((r1 + r2) + r3) + r4 and the <= 3 tail terms.
+template <int K, int UNROLL>
+__global__ __launch_bounds__(256) void dense_dot_panel_kernel(PanelDenseArgs a) {
+  __shared__ double part[4][K][kDenseColsPerBlock];
+  const int lane = threadIdx.x & 63;
+  const int k = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // chain of this wave
+  const int j = blockIdx.x * kDenseColsPerBlock + lane;
+  const int nd = a.nd;
+  const bool in_range = j < nd;
+  const int steps = a.m >> 2;
+  const int pairs = steps >> 1;
+  double acc[K];
+#pragma unroll
+  for (int v = 0; v < K; ++v) acc[v] = 0.0;
+  if (in_range) {
+    const dbl2* __restrict__ p =
+        reinterpret_cast<const dbl2*>(a.body) + static_cast<int64_t>(k) * nd + j;
+    const double* __restrict__ y = a.y + static_cast<int64_t>(k) * K;
+    const int64_t stride = static_cast<int64_t>(nd) * 4;  // double2 per pair step
+    int t = 0;
+    for (; t + UNROLL <= pairs; t += UNROLL) {
+      dbl2 x[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) x[u] = __builtin_nontemporal_load(p + (t + u) * stride);
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const double* __restrict__ y0 = y + static_cast<int64_t>(t + u) * 8 * K;
+        const double* __restrict__ y1 = y0 + 4 * K;
+#pragma unroll
+        for (int v = 0; v < K; ++v) {
+          acc[v] += x[u].x * y0[v];
+          acc[v] += x[u].y * y1[v];
+        }
+      }
+    }
+    for (; t < pairs; ++t) {
+      const dbl2 x = p[t * stride];
+      const double* __restrict__ y0 = y + static_cast<int64_t>(t) * 8 * K;
+      const double* __restrict__ y1 = y0 + 4 * K;
+#pragma unroll
+      for (int v = 0; v < K; ++v) {
+        acc[v] += x.x * y0[v];
+        acc[v] += x.y * y1[v];
+      }
+    }
+    if (steps & 1) {
+      const double x = a.body[static_cast<int64_t>(pairs) * nd * 8 +
+                              static_cast<int64_t>(k) * nd + j];
+      const double* __restrict__ y0 = y + static_cast<int64_t>(steps - 1) * 4 * K;
+#pragma unroll
+      for (int v = 0; v < K; ++v) acc[v] += x * y0[v];
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < K; ++v) part[k][v][lane] = acc[v];
+  __syncthreads();
+  if (!in_range) return;
+  const int col = a.dense_cols[j];
+  const int base = steps * 4;
+  for (int v = k; v < K && v < a.kp; v += 4) {
+    double result = part[0][v][lane] + part[1][v][lane] + part[2][v][lane] + part[3][v][lane];
+    for (int r = 0; base + r < a.m; ++r) {
+      result += a.tail[static_cast<int64_t>(r) * nd + j] *
+                a.y[static_cast<int64_t>(base + r) * K + v];
+    }
+    a.out[static_cast<int64_t>(col) * K + v] = result;
+  }
+}
+
+// out[v * ld + col] = in[col * K + v] for v < kp: a workgroup moves 64 columns
+// through LDS, so that both sides are contiguous.
+template <int K>
+__global__ __launch_bounds__(256) void deinterleave_kernel(const double* __restrict__ in,
+                                                           int ncols, int kp,
+                                                           double* __restrict__ out,
+                                                           int64_t ld) {
+  __shared__ double tile[64 * (K + 1)];
+  const int c0 = blockIdx.x * 64;
+  const int cols = min(64, ncols - c0);
+  for (int i = threadIdx.x; i < cols * K; i += 256) {
+    tile[(i / K) * (K + 1) + i % K] = in[static_cast<int64_t>(c0) * K + i];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * kp; i += 256) {
+    const int v = i >> 6;
+    const int cl = i & 63;
+    if (cl < cols) out[v * ld + c0 + cl] = tile[cl * (K + 1) + v];
+  }
+}
+
+}  // namespace milp_kernels
+
+namespace milp_launch {
+using namespace milp_kernels;
+
+static inline int panel_div_up(long a, long b) { return static_cast<int>((a + b - 1) / b); }
+
+hipError_t column_dot_panel(int width, bool long_columns, const PanelDotArgs& args,
+                            hipStream_t s) {
+  if (args.ncols <= 0) return hipSuccess;
+  if (long_columns) {
+    switch (width) {
+      case 1: column_dot_panel_long_kernel<1><<<args.ncols, 64, 0, s>>>(args); break;
+      case 4: column_dot_panel_long_kernel<4><<<args.ncols, 64, 0, s>>>(args); break;
+      case 16: column_dot_panel_long_kernel<16><<<args.ncols, 64, 0, s>>>(args); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
+  const int blocks = panel_div_up(args.ncols, 256 / (4 * width));
+  switch (width) {
+    case 1: column_dot_panel_short_kernel<1><<<blocks, 256, 0, s>>>(args); break;
+    case 4: column_dot_panel_short_kernel<4><<<blocks, 256, 0, s>>>(args); break;
+    case 16: column_dot_panel_short_kernel<16><<<blocks, 256, 0, s>>>(args); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t dense_dot_panel(int width, const PanelDenseArgs& args, hipStream_t s) {
+  if (args.nd <= 0) return hipSuccess;
+  const int blocks = panel_div_up(args.nd, kDenseColsPerBlock);
+  switch (width) {
+    case 1: dense_dot_panel_kernel<1, 8><<<blocks, 256, 0, s>>>(args); break;
+    case 4: dense_dot_panel_kernel<4, 8><<<blocks, 256, 0, s>>>(args); break;
+    case 16: dense_dot_panel_kernel<16, 4><<<blocks, 256, 0, s>>>(args); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, double* out,
+                              int64_t ld, hipStream_t s) {
+  if (ncols <= 0 || kp <= 0) return hipSuccess;
+  const int blocks = panel_div_up(ncols, 64);
+  switch (width) {
+    case 1: deinterleave_kernel<1><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
+    case 4: deinterleave_kernel<4><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
+    case 16: deinterleave_kernel<16><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace milp_launch

@@ -177,6 +177,7 @@ EXPORTED_SYMBOLS = [
     "mi_lp_set_starting_variable_values", "mi_lp_set_integrality_scale",
     "mi_lp_objective_limit_reached", "mi_lp_get_unit_row_left_inverse",
     "mi_lp_compute_dictionary", "mi_lp_get_dictionary",
+    "mi_lp_row_combinations", "mi_lp_get_tableau_rows",
     "mi_mps_read_file", "mi_mps_parse_string", "mi_mps_error", "mi_mps_dims", "mi_mps_get",
     "mi_mps_name", "mi_mps_col_name", "mi_mps_row_name", "mi_mps_free",
     "mi_lp_solver_params_default", "mi_lp_scale", "mi_lp_solver_solve",

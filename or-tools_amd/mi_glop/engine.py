@@ -114,6 +114,8 @@ def lib():
     L.mi_lp_get_unit_row_left_inverse.argtypes = [vp, ctypes.c_int32, vp, vp, vp]
     L.mi_lp_compute_dictionary.argtypes = [vp, vp, ctypes.c_int32, vp]
     L.mi_lp_get_dictionary.argtypes = [vp, vp, vp, vp]
+    L.mi_lp_row_combinations.argtypes = [vp, vp, ctypes.c_int32, vp]
+    L.mi_lp_get_tableau_rows.argtypes = [vp, vp, ctypes.c_int32, vp, vp]
     L.mi_lp_solver_params_default.argtypes = [ctypes.POINTER(abi.MiLpSolverParams)]
     L.mi_lp_scale.argtypes = [ctypes.POINTER(abi.MiLpSolverParams), ctypes.c_int32,
                               ctypes.c_int32] + [vp] * 14
@@ -494,6 +496,36 @@ class LpHandle:
         vals = np.zeros(max(1, nnz.value), np.float64)
         self._call("get_dictionary", _p(starts), _p(cols), _p(vals))
         return starts, cols[:nnz.value], vals[:nnz.value]
+
+    def row_combinations(self, Y):
+        """Y: (k, m), or (m,) for k = 1. Returns the (k, n+m) array of
+        Y[j] . a_col for every column of [A | I] (ColumnScalarProduct's order),
+        computed on the GPU with A read once per 16 vectors."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[None, :]
+        if Y.ndim != 2 or Y.shape[1] != self.lp.m:
+            raise ValueError(f"Y must be (k, {self.lp.m}), got {Y.shape}")
+        k = Y.shape[0]
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            Y = np.zeros((1, self.lp.m), np.float64)
+        out = np.zeros((max(k, 1), self.lp.n + self.lp.m), np.float64)
+        self._call("row_combinations", _p(Y), k, _p(out))
+        return out[:k]
+
+    def tableau_rows(self, rows, with_left_inverses=False):
+        """Rows `rows` of B^-1 [A | I] as a (k, n+m) array: row j is
+        unit_row_left_inverse(rows[j]) times every column. With
+        with_left_inverses also returns those (k, m) left inverses."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        k = len(rows)
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            rows = np.zeros(1, np.int32)
+        out = np.zeros((max(k, 1), self.lp.n + self.lp.m), np.float64)
+        left = np.zeros((max(k, 1), self.lp.m), np.float64) if with_left_inverses else None
+        self._call("get_tableau_rows", _p(rows), k, _p(out),
+                   None if left is None else _p(left))
+        return (out[:k], left[:k]) if with_left_inverses else out[:k]
 
 
 def batch_solve(handles, num_threads=4, progress=None, progress_s=15.0):
