@@ -289,6 +289,46 @@ int mi_lp_row_combinations(mi_lp* h, const double* y, int32_t k, double* out);
 int mi_lp_get_tableau_rows(mi_lp* h, const int32_t* rows, int32_t k, double* out,
                            double* left_inverses);
 
+/* The same rows as sparse (column, value) lists, filtered and packed on the
+ * GPU so that only the kept entries come back (a cut loop keeps the non-basic
+ * and/or structural columns above a drop tolerance). Two calls, as
+ * mi_lp_compute_dictionary / mi_lp_get_dictionary:
+ *   mi_lp_row_combinations_sparse        computes the k rows, stores them in the handle
+ *   mi_lp_get_tableau_rows_sparse        and writes row_starts (k+1; row_starts[k] is the
+ *                                        entry count). Row j holds, in strictly increasing
+ *                                        column order, every column col of [A | I] that
+ *                                        (a) passes column_filter: MI_LP_COLUMNS_STRUCTURAL
+ *                                        means col < n, MI_LP_COLUMNS_NON_BASIC means the
+ *                                        column's status in mi_lp_get_state is not
+ *                                        MI_LP_BASIC, both bits mean both, 0 every column;
+ *                                        and (b) has fabs(v) > drop_tolerance, where v is
+ *                                        bit for bit out[j (n+m) + col] of the dense call
+ *                                        above. The comparison is strict (update_row.cc's
+ *                                        fabs(acc) > drop_tolerance): at tolerance 0 both
+ *                                        +0.0 and -0.0 are dropped, a NaN result is
+ *                                        dropped, +-inf results are kept, and
+ *                                        drop_tolerance = +inf gives empty rows.
+ *   mi_lp_get_sparse_rows                copies the stored cols and vals out,
+ *                                        row_starts[k] of each. The stored result lives in
+ *                                        the handle until the next sparse call, mi_lp_load
+ *                                        or mi_lp_destroy.
+ * Errors: drop_tolerance < 0 or NaN, unknown filter bits, k < 0 or a row
+ * outside [0, m): MI_LP_ERROR_INVALID_PROBLEM with nothing written and the
+ * stored result untouched. NULL y, rows or row_starts: MI_LP_ERROR_NULL.
+ * Before a solve: MI_LP_ERROR_STATE. mi_lp_get_sparse_rows before any sparse
+ * call, or after mi_lp_load: MI_LP_ERROR_STATE. k = 0 succeeds, writes
+ * row_starts[0] = 0 and stores an empty result. Side effects on solver state
+ * are those of the dense calls: none for mi_lp_row_combinations_sparse, k
+ * mi_lp_get_unit_row_left_inverse calls for mi_lp_get_tableau_rows_sparse. */
+enum { MI_LP_COLUMNS_ALL = 0, MI_LP_COLUMNS_STRUCTURAL = 1, MI_LP_COLUMNS_NON_BASIC = 2 };
+int mi_lp_row_combinations_sparse(mi_lp* h, const double* y, int32_t k, double drop_tolerance,
+                                  uint32_t column_filter, int64_t* row_starts);
+/* left_inverses: k x m, or NULL. */
+int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
+                                  double drop_tolerance, uint32_t column_filter,
+                                  int64_t* row_starts, double* left_inverses);
+int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals);
+
 /* interrupt may be NULL; a non-zero value stops the solve like a time limit
  * (glop_interface.cc:138-140). */
 int mi_lp_solve(mi_lp* h, const volatile int32_t* interrupt, mi_lp_result* out);

@@ -61,6 +61,23 @@ typedef struct mi_devop_panel {
   int32_t width;  /* padded width of the last panel: 1, 4 or 16 */
 } mi_devop_panel;
 
+/* DeviceLp::LastPanelSparse: the last column_dots_panel_sparse. */
+typedef struct mi_devop_panel_sparse {
+  int32_t sparse; /* as mi_devop_panel */
+  int32_t dense;
+  int32_t panels;
+  int32_t width;
+  int64_t kept;       /* entries of all rows */
+  int64_t bytes_down; /* device-to-host bytes of the call */
+} mi_devop_panel_sparse;
+/* The two constants of the sparse-row kernels (kernels/kernel_args.h). */
+typedef struct mi_devop_panel_sparse_geometry {
+  int32_t tile_columns;       /* columns of one workgroup's tile */
+  int32_t offsets_step_tiles; /* tiles per block scan of the offsets kernel */
+} mi_devop_panel_sparse_geometry;
+/* column_dots_panel_sparse: the result needs more than `capacity` entries. */
+enum { MI_DEVOP_CAPACITY = 2 };
+
 typedef struct mi_devop_api {
   /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
   mi_devop* (*create)(int device, int m, int n, const int64_t* col_starts,
@@ -101,6 +118,18 @@ typedef struct mi_devop_api {
    * the list_dots kernels since the previous call (the first call turns the
    * event timing on and returns zeros). */
   int (*take_kernel_ms)(mi_devop* h, double* panel_ms, double* list_dots_ms);
+  /* Appended after take_kernel_ms. DeviceLp::ColumnDotsPanelSparse in one
+   * call: row j of the k rows keeps, columns ascending, the columns whose bit
+   * is set in keep_mask_words (ceil(N / 64) words, NULL: all) with
+   * fabs(dot) > drop_tolerance. row_starts: k + 1; cols / vals: `capacity`
+   * entries. A result of more than `capacity` entries returns
+   * MI_DEVOP_CAPACITY (last_error says how many) with row_starts, cols and
+   * vals unwritten; it is no device error. */
+  int (*column_dots_panel_sparse)(mi_devop* h, const double* y, int k, double drop_tolerance,
+                                  const uint64_t* keep_mask_words, int64_t* row_starts,
+                                  int32_t* cols, double* vals, int64_t capacity);
+  int (*last_panel_sparse)(mi_devop* h, mi_devop_panel_sparse* out);
+  int (*panel_sparse_geometry)(mi_devop_panel_sparse_geometry* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

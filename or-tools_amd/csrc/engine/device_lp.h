@@ -155,6 +155,37 @@ class DeviceLp : public DeviceSolver {
   // first call on.
   double TakePanelKernelMs();
 
+  // The same dots as sparse rows: row j keeps, in increasing column order,
+  // the columns whose bit is set in keep_words (ceil(N / 64) words, host;
+  // nullptr: every column) and whose result v has fabs(v) > drop_tolerance
+  // (strict: +-0.0 at tolerance 0 and NaN are dropped, +-inf kept). Each kept
+  // value is bit for bit what ColumnDotsPanel returns. The dot launches are
+  // ColumnDotsPanel's; then panel_count / panel_offsets / panel_write pack
+  // d_panel_i_ on the device, and only the per-vector counts and the kept
+  // (4-byte column, 8-byte value) entries come down: no transfer grows with
+  // N. Same buffers as ColumnDotsPanel plus the packed columns (4 N min(k,
+  // 16) bytes), the mask and the per-tile counts and offsets; the same
+  // solve state is left alone. Synchronizes before it returns.
+  struct SparseRows {
+    std::vector<int64_t> row_starts;  // k + 1
+    std::vector<int32_t> cols;        // row_starts[k]
+    std::vector<double> vals;
+  };
+  void ColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
+                             const uint64_t* keep_words, SparseRows* out);
+  // The last ColumnDotsPanelSparse (test record); last_panel() is not changed
+  // by it.
+  struct LastPanelSparse {
+    LastPanel panel;
+    int64_t kept = 0;        // entries of all rows
+    int64_t bytes_down = 0;  // device-to-host bytes of the call
+  };
+  LastPanelSparse last_panel_sparse() const { return last_panel_sparse_; }
+  // The sparse-row kernels' tile and the offsets kernel's scan step
+  // (kernel_args.h kPanelTileColumns, kPanelOffsetsStep), for the tests.
+  static int PanelTileColumns();
+  static int PanelOffsetsStepTiles();
+
   // --- 1 + ||a_j||^2 for relevant j (identity basis) -------------------
   void ColumnSquaredNorms(std::vector<double>* out);
 
@@ -390,6 +421,8 @@ class DeviceLp : public DeviceSolver {
   void ShardedDualBoxedFlips(const std::vector<int>* cols, double threshold,
                              std::vector<uint8_t>* flags);
   void ShardedColumnDotsPanel(const double* y, int k, double* out);
+  void ShardedColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
+                                    const uint64_t* keep_words, SparseRows* out);
   void ShardedStats();
   void FlushOwnMasks();
   // ColumnDotsPanel's own buffers (not in allocations_: they outlive a
@@ -399,9 +432,28 @@ class DeviceLp : public DeviceSolver {
   double* d_panel_y_ = nullptr;    // interleaved vectors, m x width
   double* h_panel_y_ = nullptr;    // pinned staging of it
   double* d_panel_i_ = nullptr;    // interleaved results, N x width
-  double* d_panel_out_ = nullptr;  // vector-major results, kp x N
+  double* d_panel_out_ = nullptr;  // vector-major results, kp x N; or the packed kept values
   size_t panel_y_cap_ = 0, panel_i_cap_ = 0, panel_out_cap_ = 0;  // doubles
   LastPanel last_panel_;
+  // The launch sequence both panel calls share (device_lp.hip).
+  struct PanelPlan {
+    bool long_columns = false;
+    int sparse_cols = 0;
+  };
+  PanelPlan PanelBegin();
+  void PanelDots(const PanelPlan& plan, const double* y, int first, int kp, int width);
+  void PanelKernelsLaunched();
+  void PanelDone(const PanelPlan& plan, int width, LastPanel* record);
+  // ColumnDotsPanelSparse's additions, kept like the buffers above.
+  void PanelSparseReserve(int kp, int tiles);
+  int32_t* d_panel_cols_ = nullptr;     // packed kept columns, <= N x kp
+  uint64_t* d_panel_mask_ = nullptr;    // keep mask, ceil(N / 64) words
+  int* d_panel_counts_ = nullptr;       // kp x tiles
+  int64_t* d_panel_offsets_ = nullptr;  // kp x tiles, then the kp totals
+  int64_t* h_panel_totals_ = nullptr;   // pinned, kPanelMaxWidth
+  size_t panel_cols_cap_ = 0, panel_mask_cap_ = 0, panel_counts_cap_ = 0,
+         panel_offsets_cap_ = 0;  // bytes
+  LastPanelSparse last_panel_sparse_;
   bool panel_timing_ = false;
   double panel_kernel_ms_ = 0.0;
   void* ev_panel_[2] = {nullptr, nullptr};

@@ -1649,6 +1649,16 @@ void DeviceLp::FreePanelBuffers() {
   if (h_panel_y_) (void)hipHostFree(h_panel_y_);
   d_panel_y_ = d_panel_i_ = d_panel_out_ = h_panel_y_ = nullptr;
   panel_y_cap_ = panel_i_cap_ = panel_out_cap_ = 0;
+  if (d_panel_cols_) (void)hipFree(d_panel_cols_);
+  if (d_panel_mask_) (void)hipFree(d_panel_mask_);
+  if (d_panel_counts_) (void)hipFree(d_panel_counts_);
+  if (d_panel_offsets_) (void)hipFree(d_panel_offsets_);
+  if (h_panel_totals_) (void)hipHostFree(h_panel_totals_);
+  d_panel_cols_ = nullptr;
+  d_panel_mask_ = nullptr;
+  d_panel_counts_ = nullptr;
+  d_panel_offsets_ = h_panel_totals_ = nullptr;
+  panel_cols_cap_ = panel_mask_cap_ = panel_counts_cap_ = panel_offsets_cap_ = 0;
   for (void*& e : ev_panel_) {
     if (e) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(e));
     e = nullptr;
@@ -1688,15 +1698,15 @@ double DeviceLp::TakePanelKernelMs() {
   return ms;
 }
 
-void DeviceLp::ColumnDotsPanel(const double* y, int k, double* out) {
-  if (!shards_.empty()) return ShardedColumnDotsPanel(y, k, out);
-  last_panel_ = LastPanel();
-  if (k <= 0 || n_total_ <= 0) return;
-  DeviceOp("column dots panel");
+// What the dense and the sparse panel call share: the kernel choice
+// (LaunchColumnDots' rule) and the timing events, then per panel the y
+// interleave, its upload and the dot launches into d_panel_i_.
+DeviceLp::PanelPlan DeviceLp::PanelBegin() {
+  PanelPlan plan;
   const double sparse_avg =
       (nd_ > 0 ? (ns_ > 0 ? double(sparse_entries_) / ns_ : 0.0) : avg_col_len_);
-  const bool long_columns = sparse_avg >= 32.0;  // LaunchColumnDots' rule
-  const int sparse_cols = nd_ > 0 ? ns_ : n_total_;
+  plan.long_columns = sparse_avg >= 32.0;  // LaunchColumnDots' rule
+  plan.sparse_cols = nd_ > 0 ? ns_ : n_total_;
   if (panel_timing_ && ev_panel_[0] == nullptr) {
     for (void*& e : ev_panel_) {
       hipEvent_t ev;
@@ -1704,63 +1714,183 @@ void DeviceLp::ColumnDotsPanel(const double* y, int k, double* out) {
       e = ev;
     }
   }
+  return plan;
+}
+
+void DeviceLp::PanelDots(const PanelPlan& plan, const double* y, int first, int kp, int width) {
+  PanelReserve(width, kp);
+  for (int r = 0; r < m_; ++r) {
+    double* dst = h_panel_y_ + size_t(r) * width;
+    for (int v = 0; v < kp; ++v) dst[v] = y[size_t(first + v) * m_ + r];
+    for (int v = kp; v < width; ++v) dst[v] = 0.0;
+  }
+  Upload(d_panel_y_, h_panel_y_, size_t(m_) * width * sizeof(double));
+  if (panel_timing_) {
+    Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
+  }
+  milp_kernels::PanelDotArgs a{};
+  a.starts = d_starts_;
+  a.rows = d_rows_;
+  a.vals = d_vals_;
+  a.y = d_panel_y_;
+  a.ncols = plan.sparse_cols;
+  a.col_list = nd_ > 0 ? d_sparse_cols_ : nullptr;
+  a.kp = kp;
+  a.out = d_panel_i_;
+  Check(milp_launch::column_dot_panel(width, plan.long_columns, a, S(stream_)),
+        "column dots panel");
+  if (nd_ > 0) {
+    milp_kernels::PanelDenseArgs d{};
+    d.body = d_dense_body_;
+    d.tail = d_dense_tail_;
+    d.dense_cols = d_dense_cols_;
+    d.nd = nd_;
+    d.m = m_;
+    d.y = d_panel_y_;
+    d.kp = kp;
+    d.out = d_panel_i_;
+    Check(milp_launch::dense_dot_panel(width, d, S(stream_)), "dense dots panel");
+  }
+}
+
+// After the panel's last kernel launch, before its synchronizing download.
+void DeviceLp::PanelKernelsLaunched() {
+  if (panel_timing_) {
+    Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[1]), S(stream_)), "ev");
+  }
+}
+
+// After that download: the kernel time and the record of the panel.
+void DeviceLp::PanelDone(const PanelPlan& plan, int width, LastPanel* record) {
+  if (panel_timing_) {
+    float ms = 0.0f;
+    Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(ev_panel_[0]),
+                              reinterpret_cast<hipEvent_t>(ev_panel_[1])),
+          "ev time");
+    panel_kernel_ms_ += ms;
+  }
+  record->sparse = plan.sparse_cols > 0
+                       ? (plan.long_columns ? kPanelLongColumns : kPanelShortColumns)
+                       : kPanelNone;
+  record->dense = nd_ > 0;
+  record->panels += 1;
+  record->width = width;
+}
+
+static int PanelWidth(int kp) { return kp == 1 ? 1 : (kp <= 4 ? 4 : 16); }
+
+void DeviceLp::ColumnDotsPanel(const double* y, int k, double* out) {
+  if (!shards_.empty()) return ShardedColumnDotsPanel(y, k, out);
+  last_panel_ = LastPanel();
+  if (k <= 0 || n_total_ <= 0) return;
+  DeviceOp("column dots panel");
+  const PanelPlan plan = PanelBegin();
   for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
     const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
-    const int width = kp == 1 ? 1 : (kp <= 4 ? 4 : 16);
-    PanelReserve(width, kp);
-    for (int r = 0; r < m_; ++r) {
-      double* dst = h_panel_y_ + size_t(r) * width;
-      for (int v = 0; v < kp; ++v) dst[v] = y[size_t(first + v) * m_ + r];
-      for (int v = kp; v < width; ++v) dst[v] = 0.0;
-    }
-    Upload(d_panel_y_, h_panel_y_, size_t(m_) * width * sizeof(double));
-    if (panel_timing_) {
-      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
-    }
-    milp_kernels::PanelDotArgs a{};
-    a.starts = d_starts_;
-    a.rows = d_rows_;
-    a.vals = d_vals_;
-    a.y = d_panel_y_;
-    a.ncols = sparse_cols;
-    a.col_list = nd_ > 0 ? d_sparse_cols_ : nullptr;
-    a.kp = kp;
-    a.out = d_panel_i_;
-    Check(milp_launch::column_dot_panel(width, long_columns, a, S(stream_)), "column dots panel");
-    if (nd_ > 0) {
-      milp_kernels::PanelDenseArgs d{};
-      d.body = d_dense_body_;
-      d.tail = d_dense_tail_;
-      d.dense_cols = d_dense_cols_;
-      d.nd = nd_;
-      d.m = m_;
-      d.y = d_panel_y_;
-      d.kp = kp;
-      d.out = d_panel_i_;
-      Check(milp_launch::dense_dot_panel(width, d, S(stream_)), "dense dots panel");
-    }
+    const int width = PanelWidth(kp);
+    PanelDots(plan, y, first, kp, width);
     Check(milp_launch::panel_deinterleave(width, d_panel_i_, n_total_, kp, d_panel_out_,
                                           n_total_, S(stream_)),
           "panel de-interleave");
-    if (panel_timing_) {
-      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[1]), S(stream_)), "ev");
-    }
+    PanelKernelsLaunched();
     Download(out + size_t(first) * n_total_, d_panel_out_,
              size_t(kp) * n_total_ * sizeof(double));
-    if (panel_timing_) {
-      float ms = 0.0f;
-      Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(ev_panel_[0]),
-                                reinterpret_cast<hipEvent_t>(ev_panel_[1])),
-            "ev time");
-      panel_kernel_ms_ += ms;
-    }
-    last_panel_.sparse = sparse_cols > 0 ? (long_columns ? kPanelLongColumns : kPanelShortColumns)
-                                         : kPanelNone;
-    last_panel_.dense = nd_ > 0;
-    last_panel_.panels += 1;
-    last_panel_.width = width;
+    PanelDone(plan, width, &last_panel_);
   }
   DeviceOp("column dots panel done");
+}
+
+int DeviceLp::PanelTileColumns() { return milp_kernels::kPanelTileColumns; }
+int DeviceLp::PanelOffsetsStepTiles() { return milp_kernels::kPanelOffsetsStep; }
+
+// Grows the sparse form's own buffers to one panel of kp vectors: the packed
+// columns (d_panel_out_ holds the packed values), the keep mask, the per
+// (vector, tile) counts and offsets with the kp totals behind the offsets, and
+// the pinned landing place of the totals.
+void DeviceLp::PanelSparseReserve(int kp, int tiles) {
+  const auto grow = [this](void** p, size_t* cap, size_t bytes, const char* what) {
+    if (bytes <= *cap) return;
+    if (*p) Check(hipFree(*p), what);
+    *p = nullptr;
+    *cap = 0;
+    Check(hipMalloc(p, bytes), what);
+    *cap = bytes;
+  };
+  grow(reinterpret_cast<void**>(&d_panel_cols_), &panel_cols_cap_,
+       size_t(n_total_) * kp * sizeof(int32_t), "panel columns");
+  grow(reinterpret_cast<void**>(&d_panel_mask_), &panel_mask_cap_,
+       size_t((n_total_ + 63) / 64) * sizeof(uint64_t), "panel mask");
+  grow(reinterpret_cast<void**>(&d_panel_counts_), &panel_counts_cap_,
+       size_t(kp) * tiles * sizeof(int), "panel counts");
+  grow(reinterpret_cast<void**>(&d_panel_offsets_), &panel_offsets_cap_,
+       (size_t(kp) * tiles + milp_kernels::kPanelMaxWidth) * sizeof(int64_t), "panel offsets");
+  if (h_panel_totals_ == nullptr) {
+    Check(hipHostMalloc(reinterpret_cast<void**>(&h_panel_totals_),
+                        milp_kernels::kPanelMaxWidth * sizeof(int64_t)),
+          "panel totals");
+  }
+}
+
+void DeviceLp::ColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
+                                     const uint64_t* keep_words, SparseRows* out) {
+  if (!shards_.empty()) {
+    return ShardedColumnDotsPanelSparse(y, k, drop_tolerance, keep_words, out);
+  }
+  last_panel_sparse_ = LastPanelSparse();
+  out->row_starts.assign(size_t(std::max(k, 0)) + 1, 0);
+  out->cols.clear();
+  out->vals.clear();
+  if (k <= 0 || n_total_ <= 0) return;
+  DeviceOp("column dots panel sparse");
+  const PanelPlan plan = PanelBegin();
+  const int tiles = (n_total_ + milp_kernels::kPanelTileColumns - 1) /
+                    milp_kernels::kPanelTileColumns;
+  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
+    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
+    const int width = PanelWidth(kp);
+    PanelDots(plan, y, first, kp, width);
+    PanelSparseReserve(kp, tiles);
+    if (first == 0 && keep_words != nullptr) {
+      Upload(d_panel_mask_, keep_words, size_t((n_total_ + 63) / 64) * sizeof(uint64_t));
+    }
+    milp_kernels::PanelSparseArgs a{};
+    a.in = d_panel_i_;
+    a.ncols = n_total_;
+    a.kp = kp;
+    a.tiles = tiles;
+    a.mask = keep_words != nullptr ? d_panel_mask_ : nullptr;
+    a.drop_tolerance = drop_tolerance;
+    a.counts = d_panel_counts_;
+    a.offsets = d_panel_offsets_;
+    a.totals = d_panel_offsets_ + size_t(kp) * tiles;
+    a.cols = d_panel_cols_;
+    a.vals = d_panel_out_;
+    Check(milp_launch::panel_sparse(width, a, S(stream_)), "panel sparse rows");
+    PanelKernelsLaunched();
+    // Down: the kp totals, then exactly the kept entries.
+    Download(h_panel_totals_, a.totals, size_t(kp) * sizeof(int64_t));
+    int64_t kept = 0;
+    for (int v = 0; v < kp; ++v) {
+      if (h_panel_totals_[v] < 0 || h_panel_totals_[v] > n_total_) {
+        throw DeviceError("panel sparse rows: bad count");
+      }
+      kept += h_panel_totals_[v];
+      out->row_starts[first + v + 1] = out->row_starts[first + v] + h_panel_totals_[v];
+    }
+    const size_t old = out->cols.size();
+    out->cols.resize(old + size_t(kept));
+    out->vals.resize(old + size_t(kept));
+    if (kept > 0) {
+      Check(hipMemcpyAsync(out->cols.data() + old, d_panel_cols_, size_t(kept) * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+      Download(out->vals.data() + old, d_panel_out_, size_t(kept) * sizeof(double));
+    }
+    PanelDone(plan, width, &last_panel_sparse_.panel);
+    last_panel_sparse_.kept += kept;
+    last_panel_sparse_.bytes_down += int64_t(kp) * 8 + kept * 12;
+  }
+  DeviceOp("column dots panel sparse done");
 }
 
 void DeviceLp::ColumnSquaredNorms(std::vector<double>* out) {

@@ -240,6 +240,46 @@ int TakeKernelMs(mi_devop* h, double* panel_ms, double* list_dots_ms) {
   });
 }
 
+int ColumnDotsPanelSparse(mi_devop* h, const double* y, int k, double drop_tolerance,
+                          const uint64_t* keep_mask_words, int64_t* row_starts, int32_t* cols,
+                          double* vals, int64_t capacity) {
+  bool too_large = false;
+  const int rc = Guard(h, [&] {
+    milp::DeviceLp::SparseRows rows;
+    h->dev.ColumnDotsPanelSparse(y, k, drop_tolerance, keep_mask_words, &rows);
+    const int64_t kept = rows.row_starts.back();
+    if (kept > capacity) {
+      too_large = true;
+      throw milp::DeviceError("column_dots_panel_sparse: " + std::to_string(kept) +
+                              " entries, capacity " + std::to_string(capacity));
+    }
+    std::memcpy(row_starts, rows.row_starts.data(), rows.row_starts.size() * sizeof(int64_t));
+    if (kept > 0) {
+      std::memcpy(cols, rows.cols.data(), size_t(kept) * sizeof(int32_t));
+      std::memcpy(vals, rows.vals.data(), size_t(kept) * sizeof(double));
+    }
+  });
+  return too_large ? int{MI_DEVOP_CAPACITY} : rc;
+}
+
+int LastPanelSparse(mi_devop* h, mi_devop_panel_sparse* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastPanelSparse p = h->dev.last_panel_sparse();
+    out->sparse = p.panel.sparse;
+    out->dense = p.panel.dense ? 1 : 0;
+    out->panels = p.panel.panels;
+    out->width = p.panel.width;
+    out->kept = p.kept;
+    out->bytes_down = p.bytes_down;
+  });
+}
+
+int PanelSparseGeometry(mi_devop_panel_sparse_geometry* out) {
+  out->tile_columns = milp::DeviceLp::PanelTileColumns();
+  out->offsets_step_tiles = milp::DeviceLp::PanelOffsetsStepTiles();
+  return 0;
+}
+
 static_assert(int{MI_DEVOP_PANEL_LONG_COLUMNS} == int{milp::DeviceLp::kPanelLongColumns},
               "mi_lp_devop.h restates DeviceLp's panel shapes");
 static_assert(int{MI_DEVOP_ROW_COLUMN_WISE_GENERAL} == int{milp::DeviceLp::kRowColumnWiseGeneral} &&
@@ -263,4 +303,6 @@ extern "C" const mi_devop_api mi_devop_table = {
     LastPaths,
     ColumnDotsPanel,  LastPanel,
     TakeKernelMs,
+    ColumnDotsPanelSparse, LastPanelSparse,
+    PanelSparseGeometry,
 };

@@ -450,6 +450,77 @@ void DeviceLp::ShardedColumnDotsPanel(const double* y, int k, double* out) {
   }
 }
 
+// Each block's sparse rows over its own columns (the keep mask re-cut at the
+// block's first column), joined per vector in block order with the block's
+// first column added: increasing columns again. The parts travel through
+// ExchangeParts like ShardedColumnDotsPanel's.
+void DeviceLp::ShardedColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
+                                            const uint64_t* keep_words, SparseRows* out) {
+  DeviceGuard guard{device_};
+  last_panel_sparse_ = LastPanelSparse();
+  out->row_starts.assign(size_t(std::max(k, 0)) + 1, 0);
+  out->cols.clear();
+  out->vals.clear();
+  if (k <= 0) return;
+  const int ns = num_shards();
+  std::vector<std::string> parts(ns);
+  std::vector<SparseRows> rows(ns);
+  std::vector<uint64_t> words;
+  for (int s = 0; s < ns; ++s) {
+    if (!IsLocalShard(s)) continue;
+    DeviceLp& d = Shard(s);
+    SparseRows& part = rows[s];
+    part.row_starts.assign(size_t(k) + 1, 0);
+    if (d.n_total_ > 0) {
+      if (keep_words != nullptr) {
+        const int b = shard_begin_[s];
+        words.assign(size_t(d.n_total_ + 63) / 64, 0);
+        for (int c = 0; c < d.n_total_; ++c) {
+          const int g = b + c;
+          if ((keep_words[g >> 6] >> (g & 63)) & 1ull) words[c >> 6] |= 1ull << (c & 63);
+        }
+      }
+      d.ColumnDotsPanelSparse(y, k, drop_tolerance, keep_words != nullptr ? words.data() : nullptr,
+                              &part);
+      const LastPanelSparse p = d.last_panel_sparse();
+      last_panel_sparse_.panel.sparse = std::max(last_panel_sparse_.panel.sparse, p.panel.sparse);
+      last_panel_sparse_.panel.dense = last_panel_sparse_.panel.dense || p.panel.dense;
+      last_panel_sparse_.panel.panels = p.panel.panels;
+      last_panel_sparse_.panel.width = p.panel.width;
+      last_panel_sparse_.kept += p.kept;
+      last_panel_sparse_.bytes_down += p.bytes_down;
+    }
+    PartWriter w;
+    w.Put(part.row_starts);
+    w.Put(part.cols);
+    w.Put(part.vals);
+    parts[s] = std::move(w.b);
+  }
+  ExchangeParts(&parts);
+  for (int s = 0; s < ns; ++s) {
+    PartReader r{parts[s]};
+    r.Get(&rows[s].row_starts);
+    r.Get(&rows[s].cols);
+    r.Get(&rows[s].vals);
+    const SparseRows& p = rows[s];
+    if (p.row_starts.size() != size_t(k) + 1 || p.row_starts[0] != 0 ||
+        p.cols.size() != size_t(p.row_starts[k]) || p.vals.size() != p.cols.size()) {
+      throw DeviceError("column split: bad sparse panel part");
+    }
+  }
+  for (int j = 0; j < k; ++j) {
+    for (int s = 0; s < ns; ++s) {
+      const SparseRows& p = rows[s];
+      const int32_t base = shard_begin_[s];
+      for (int64_t i = p.row_starts[j]; i < p.row_starts[j + 1]; ++i) {
+        out->cols.push_back(p.cols[i] + base);
+        out->vals.push_back(p.vals[i]);
+      }
+    }
+    out->row_starts[j + 1] = static_cast<int64_t>(out->cols.size());
+  }
+}
+
 void DeviceLp::ShardedDualBegin(const std::vector<double>& rc,
                                 const std::vector<uint8_t>& colbits,
                                 const std::vector<double>& bound_diff) {

@@ -5714,6 +5714,8 @@ Status RevisedSimplex::PrimalPush(TimeLimit* time_limit) {
 struct mi_lp {
   milp::RevisedSimplex simplex;
   std::vector<std::vector<std::pair<int, double>>> dictionary;  // mi_lp_compute_dictionary
+  milp::DeviceLp::SparseRows sparse_rows;  // the last mi_lp_*_sparse result
+  bool sparse_rows_stored = false;
   milp::GlopParameters params;
   milp::LinearProgram lp;
   int device = 0;
@@ -6051,6 +6053,7 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t*
   if (m < 0 || n < 0) return MI_LP_ERROR_INVALID_PROBLEM;
   if (h->running) return MI_LP_ERROR_STATE;
   if (cs[n] > 0 && (ri == nullptr || vals == nullptr)) return MI_LP_ERROR_NULL;
+  h->sparse_rows_stored = false;  // mi_lp_get_sparse_rows: rows of the LP before
   if ((n > 0 && (clb == nullptr || cub == nullptr || obj == nullptr)) ||
       (m > 0 && (rlb == nullptr || rub == nullptr))) {
     return MI_LP_ERROR_NULL;
@@ -6275,6 +6278,109 @@ int mi_lp_get_tableau_rows(mi_lp* h, const int32_t* rows, int32_t k, double* out
   } catch (const std::exception& e) {
     h->error = e.what();
     return MI_LP_ERROR_INTERNAL;
+  }
+  return MI_LP_OK;
+}
+
+namespace {
+// The argument checks the two sparse calls share; MI_LP_OK when they pass.
+int CheckSparseRowArgs(const mi_lp* h, int32_t k, double drop_tolerance, uint32_t column_filter) {
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0 || !(drop_tolerance >= 0.0) ||
+      (column_filter & ~uint32_t{MI_LP_COLUMNS_STRUCTURAL | MI_LP_COLUMNS_NON_BASIC}) != 0) {
+    return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  return MI_LP_OK;
+}
+
+// y (k x m) -> the stored sparse rows and row_starts. The keep mask is built
+// here from the solver's statuses (mi_lp_get_state's), not read from the
+// device's masks.
+void StoreSparseRows(mi_lp* h, const double* y, int32_t k, double drop_tolerance,
+                     uint32_t column_filter, int64_t* row_starts) {
+  const int n = h->lp.n;
+  const int total = n + h->lp.m;
+  std::vector<uint64_t> words;
+  if (column_filter != MI_LP_COLUMNS_ALL) {
+    words.assign(size_t(total + 63) / 64, 0);
+    const auto& state = h->simplex.GetState();
+    for (int col = 0; col < total; ++col) {
+      if ((column_filter & MI_LP_COLUMNS_STRUCTURAL) != 0 && col >= n) continue;
+      if ((column_filter & MI_LP_COLUMNS_NON_BASIC) != 0 &&
+          (size_t(col) >= state.size() || state[col] == milp::VariableStatus::BASIC)) {
+        continue;
+      }
+      words[col >> 6] |= 1ull << (col & 63);
+    }
+  }
+  milp::DeviceLp::SparseRows rows;
+  h->simplex.device().ColumnDotsPanelSparse(y, k, drop_tolerance,
+                                            words.empty() ? nullptr : words.data(), &rows);
+  h->sparse_rows = std::move(rows);
+  h->sparse_rows_stored = true;
+  for (int32_t j = 0; j <= k; ++j) row_starts[j] = h->sparse_rows.row_starts[j];
+}
+}  // namespace
+
+int mi_lp_row_combinations_sparse(mi_lp* h, const double* y, int32_t k, double drop_tolerance,
+                                  uint32_t column_filter, int64_t* row_starts) {
+  if (h == nullptr || y == nullptr || row_starts == nullptr) return MI_LP_ERROR_NULL;
+  const int bad = CheckSparseRowArgs(h, k, drop_tolerance, column_filter);
+  if (bad != MI_LP_OK) return bad;
+  try {
+    (void)hipSetDevice(h->device);
+    StoreSparseRows(h, y, k, drop_tolerance, column_filter, row_starts);
+  } catch (const milp::DeviceError& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+  return MI_LP_OK;
+}
+
+int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
+                                  double drop_tolerance, uint32_t column_filter,
+                                  int64_t* row_starts, double* left_inverses) {
+  if (h == nullptr || rows == nullptr || row_starts == nullptr) return MI_LP_ERROR_NULL;
+  const int bad = CheckSparseRowArgs(h, k, drop_tolerance, column_filter);
+  if (bad != MI_LP_OK) return bad;
+  const int m = h->lp.m;
+  for (int32_t j = 0; j < k; ++j) {
+    if (rows[j] < 0 || rows[j] >= m) return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  try {
+    (void)hipSetDevice(h->device);
+    // As mi_lp_get_tableau_rows: k host left solves in the caller's order.
+    std::vector<double> local;
+    double* y = left_inverses;
+    if (y == nullptr) {
+      local.resize(std::max<size_t>(1, size_t(k) * m));
+      y = local.data();
+    }
+    for (int32_t j = 0; j < k; ++j) {
+      const milp::ScatteredVector& v = h->simplex.GetUnitRowLeftInverse(rows[j]);
+      for (int r = 0; r < m; ++r) y[size_t(j) * m + r] = v.values[r];
+    }
+    StoreSparseRows(h, y, k, drop_tolerance, column_filter, row_starts);
+  } catch (const milp::DeviceError& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+  return MI_LP_OK;
+}
+
+int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals) {
+  if (h == nullptr || cols == nullptr || vals == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->sparse_rows_stored) return MI_LP_ERROR_STATE;
+  const size_t kept = h->sparse_rows.cols.size();
+  if (kept > 0) {
+    std::memcpy(cols, h->sparse_rows.cols.data(), kept * sizeof(int32_t));
+    std::memcpy(vals, h->sparse_rows.vals.data(), kept * sizeof(double));
   }
   return MI_LP_OK;
 }

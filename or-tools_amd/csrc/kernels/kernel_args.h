@@ -75,6 +75,27 @@ struct PanelDenseArgs {  // the dense block of DenseArgs
   double* out;
 };
 
+// The panel result filtered and packed into sparse rows (panel_kernels.hip,
+// panel_count / panel_offsets / panel_write). Entry (col, v) is kept when
+// the column's mask bit is set (mask == nullptr: every column) and
+// fabs(in[col * K + v]) > drop_tolerance. Vector v's kept entries, columns
+// ascending, start at the sum of totals[0 .. v) in cols / vals.
+constexpr int kPanelTileColumns = 256;  // columns of one workgroup's tile
+constexpr int kPanelOffsetsStep = 256;  // tiles per block scan of panel_offsets
+struct PanelSparseArgs {
+  const double* in;      // interleaved panel result, ncols x K
+  int ncols;
+  int kp;                // vectors in use (<= K)
+  int tiles;             // ceil(ncols / kPanelTileColumns)
+  const uint64_t* mask;  // ceil(ncols / 64) words, or nullptr
+  double drop_tolerance;
+  int* counts;           // kp x tiles
+  int64_t* offsets;      // kp x tiles
+  int64_t* totals;       // kp
+  int32_t* cols;         // packed output; room for ncols * kp entries
+  double* vals;
+};
+
 // Where an update-row kernel that emits the list itself puts it: the
 // ascending listed columns, their coefficients and the count, on the device
 // and (optional, null when off) mirrored into mapped host memory.
@@ -452,6 +473,8 @@ hipError_t dense_dot_panel(int width, const milp_kernels::PanelDenseArgs& args, 
 // out[v * ld + col] = in[col * width + v] for v < kp, col < ncols.
 hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, double* out,
                               int64_t ld, hipStream_t s);
+// panel_count, panel_offsets and panel_write for one panel, in that order.
+hipError_t panel_sparse(int width, const milp_kernels::PanelSparseArgs& args, hipStream_t s);
 hipError_t dense_pack(const int64_t* starts, const double* vals, const int32_t* dense_cols,
                       int nd, int m, double* body, double* tail, hipStream_t s);
 hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hipStream_t s);

@@ -12,15 +12,20 @@
 // entry meets are contiguous. Results go to out[col * K + v] (a column's K
 // results contiguous); deinterleave_kernel turns that into the caller's
 // vector-major rows. Only vectors v < kp are stored (the others are padding).
+//
+// The sparse form (panel_count / panel_offsets / panel_write, at the end)
+// filters out[col * K + v] by a column mask and a drop tolerance and packs
+// the kept (column, value) pairs per vector in increasing column order; it
+// replaces deinterleave_kernel when the caller wants sparse rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_scan.h"
 #include "kernel_args.h"
 
 namespace milp_kernels {
 
 namespace {
-constexpr int kWave = 64;
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 constexpr int kDenseColsPerBlock = 64;
 }  // namespace
@@ -208,6 +213,139 @@ __global__ __launch_bounds__(256) void deinterleave_kernel(const double* __restr
   }
 }
 
+// ---------------------------------------------------------------------------
+// Sparse rows out of the interleaved panel result, in three launches on one
+// stream; no workgroup waits for another.
+//   panel_count    a workgroup owns a tile of kPanelTileColumns consecutive
+//                  columns and counts the kept entries of every vector in it:
+//                  counts[v * tiles + tile].
+//   panel_offsets  one workgroup turns the counts into where each (vector,
+//                  tile) starts in the packed output, vector v right after
+//                  v - 1, and writes the per-vector totals.
+//   panel_write    the count kernel's tiles again: the kept entries of
+//                  (vector, tile) go to cols / vals from that start on, in
+//                  increasing column order.
+// The tile's kPanelTileColumns * K doubles are contiguous in `in`; thread t
+// reads elements t, t + 256, ... (coalesced). K divides 256, so a thread
+// meets one vector only, v = t % K, at columns t / K + j * (256 / K).
+
+// The keep rule of both kernels: the column passes the mask and |x| exceeds
+// the tolerance. The comparison is false for a NaN and for +-0.0 at tolerance
+// 0, true for +-inf unless the tolerance is +inf.
+__device__ __forceinline__ bool panel_keep(double x, bool masked_in, double drop_tolerance) {
+  return masked_in && fabs(x) > drop_tolerance;
+}
+
+__device__ __forceinline__ bool panel_mask_bit(const uint64_t* __restrict__ mask, int col) {
+  return mask == nullptr || ((mask[col >> 6] >> (col & 63)) & 1ull) != 0;
+}
+
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void panel_count_kernel(PanelSparseArgs a) {
+  static_assert(kPanelTileColumns == 256 && kPanelTileColumns % K == 0 && kWave % K == 0,
+                "a thread owns one vector");
+  __shared__ int cnt[K];
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int col0 = tile * kPanelTileColumns;
+  const int cols = min(kPanelTileColumns, a.ncols - col0);
+  if (t < K) cnt[t] = 0;
+  __syncthreads();
+  const double* __restrict__ in = a.in + static_cast<int64_t>(col0) * K;
+  const int v = t % K;
+  int c = 0;
+  if (v < a.kp) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int cl = t / K + j * (kPanelTileColumns / K);
+      if (cl < cols) {
+        const double x = in[t + j * kPanelTileColumns];
+        c += panel_keep(x, panel_mask_bit(a.mask, col0 + cl), a.drop_tolerance) ? 1 : 0;
+      }
+    }
+  }
+  // Lanes l, l + K, l + 2K, ... of a wave hold the same vector.
+#pragma unroll
+  for (int off = K; off < kWave; off <<= 1) c += __shfl_xor(c, off, kWave);
+  if ((t & (kWave - 1)) < K && v < a.kp) atomicAdd(&cnt[v], c);
+  __syncthreads();
+  if (t < a.kp) a.counts[static_cast<int64_t>(t) * a.tiles + tile] = cnt[t];
+}
+
+// offsets[v * tiles + tile] = kept entries of the vectors before v + those of
+// v's tiles before `tile`; totals[v] = v's kept entries. One workgroup: per
+// vector, a block scan per step of kPanelOffsetsStep tiles with the running
+// total carried in a register (every thread computes the same one).
+__global__ __launch_bounds__(kPanelOffsetsStep) void panel_offsets_kernel(PanelSparseArgs a) {
+  __shared__ int lds_waves[kPanelOffsetsStep / kWave];
+  const int t = threadIdx.x;
+  int64_t running = 0;
+  for (int v = 0; v < a.kp; ++v) {
+    const int64_t begin = running;
+    const int64_t row = static_cast<int64_t>(v) * a.tiles;
+    for (int base = 0; base < a.tiles; base += kPanelOffsetsStep) {
+      const int tile = base + t;
+      const int c = tile < a.tiles ? a.counts[row + tile] : 0;
+      int total;
+      const int excl = scan_block_exclusive<kPanelOffsetsStep>(c, &total, lds_waves);
+      if (tile < a.tiles) a.offsets[row + tile] = running + excl;
+      running += total;
+      __syncthreads();  // the next scan goes through the same lds_waves
+    }
+    if (t == 0) a.totals[v] = running - begin;
+  }
+}
+
+// The tile is transposed through LDS, tile[v][column], so that a wave then
+// reads 64 consecutive columns of one vector. Row stride: the ds_write_b64 of
+// the staging pass is served in groups of 16 lanes over 32 banks, and a group
+// holds 16 / K columns of K vectors each, at dword 2 * (v * stride + column):
+// stride = 257 (K = 16) and 260 (K = 4) give every lane of a group its own
+// bank pair; the row reads are consecutive doubles and conflict-free at any
+// stride. Wave w then takes the vectors w, w + 4, ... < kp: per 64 columns a
+// ballot of the keep rule, rank = the kept lanes below + the kept columns of
+// the chunks before.
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void panel_write_kernel(PanelSparseArgs a) {
+  constexpr int kStride = kPanelTileColumns + (K == 1 ? 0 : 16 / K);
+  __shared__ double tile_vals[K * kStride];
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int col0 = tile * kPanelTileColumns;
+  const int cols = min(kPanelTileColumns, a.ncols - col0);
+  const double* __restrict__ in = a.in + static_cast<int64_t>(col0) * K;
+  {
+    const int v = t % K;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int cl = t / K + j * (kPanelTileColumns / K);
+      if (cl < cols && v < a.kp) tile_vals[v * kStride + cl] = in[t + j * kPanelTileColumns];
+    }
+  }
+  __syncthreads();
+  const int lane = t & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(t / kWave);
+  for (int v = wave; v < a.kp; v += kPanelTileColumns / kWave) {
+    int64_t pos = a.offsets[static_cast<int64_t>(v) * a.tiles + tile];
+    for (int chunk = 0; chunk * kWave < cols; ++chunk) {
+      const int cl = chunk * kWave + lane;
+      double x = 0.0;
+      bool keep = false;
+      if (cl < cols) {
+        x = tile_vals[v * kStride + cl];
+        keep = panel_keep(x, panel_mask_bit(a.mask, col0 + cl), a.drop_tolerance);
+      }
+      const unsigned long long kept = __ballot(keep);
+      if (keep) {
+        const int64_t at = pos + __popcll(kept & ((1ull << lane) - 1ull));
+        a.cols[at] = col0 + cl;
+        a.vals[at] = x;
+      }
+      pos += __popcll(kept);
+    }
+  }
+}
+
 }  // namespace milp_kernels
 
 namespace milp_launch {
@@ -258,6 +396,24 @@ hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, do
     case 4: deinterleave_kernel<4><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
     case 16: deinterleave_kernel<16><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
     default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t panel_sparse(int width, const PanelSparseArgs& args, hipStream_t s) {
+  if (args.ncols <= 0 || args.kp <= 0) return hipSuccess;
+  if (args.tiles != panel_div_up(args.ncols, kPanelTileColumns)) return hipErrorInvalidValue;
+  switch (width) {
+    case 1: panel_count_kernel<1><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
+    case 4: panel_count_kernel<4><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
+    case 16: panel_count_kernel<16><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
+    default: return hipErrorInvalidValue;
+  }
+  panel_offsets_kernel<<<1, kPanelOffsetsStep, 0, s>>>(args);
+  switch (width) {
+    case 1: panel_write_kernel<1><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
+    case 4: panel_write_kernel<4><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
+    default: panel_write_kernel<16><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
   }
   return hipGetLastError();
 }

@@ -12,11 +12,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "block_scan.h"
 #include "kernel_args.h"
 
 namespace milp_kernels {
-
-constexpr int kWave = 64;
 
 __device__ __forceinline__ bool bit_set(const uint64_t* words, int i) {
   return (words[i >> 6] >> (i & 63)) & 1ull;
@@ -327,35 +326,8 @@ __global__ void gather_kernel(const int32_t* list, int n, const double* src, dou
 
 // ---------------------------------------------------------------------------
 // The pieces every update-row kernel that emits its list shares: the block
-// scan that places the listed columns, and the two stores into a ListOut.
-
-// Block-wide exclusive scan of one int per thread (THREADS threads, all of
-// them call it); *total = the sum over the block. lds_waves holds THREADS /
-// kWave ints. The only barrier sits between writing and reading lds_waves:
-// a caller that scans twice through the same lds_waves owns a barrier between
-// the two calls (a slow wave may still be reading the first call's sums).
-template <int THREADS = kScanThreads>
-__device__ __forceinline__ int scan_block_exclusive(int c, int* total, int* lds_waves) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  int x = c;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int y = __shfl_up(x, off, kWave);
-    if (lane >= off) x += y;
-  }
-  if (lane == kWave - 1) lds_waves[wave] = x;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < THREADS / kWave; ++w) {
-    const int v = lds_waves[w];
-    before += w < wave ? v : 0;
-    all += v;
-  }
-  *total = all;
-  return before + x - c;
-}
+// scan that places the listed columns (scan_block_exclusive, block_scan.h),
+// and the two stores into a ListOut.
 
 // List slot `pos` = (col, v); the mapped host mirror is the zero-copy readback.
 __device__ __forceinline__ void list_store(const ListOut& o, int pos, int32_t col, double v) {

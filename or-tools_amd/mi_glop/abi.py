@@ -178,6 +178,7 @@ EXPORTED_SYMBOLS = [
     "mi_lp_objective_limit_reached", "mi_lp_get_unit_row_left_inverse",
     "mi_lp_compute_dictionary", "mi_lp_get_dictionary",
     "mi_lp_row_combinations", "mi_lp_get_tableau_rows",
+    "mi_lp_row_combinations_sparse", "mi_lp_get_tableau_rows_sparse", "mi_lp_get_sparse_rows",
     "mi_mps_read_file", "mi_mps_parse_string", "mi_mps_error", "mi_mps_dims", "mi_mps_get",
     "mi_mps_name", "mi_mps_col_name", "mi_mps_row_name", "mi_mps_free",
     "mi_lp_solver_params_default", "mi_lp_scale", "mi_lp_solver_solve",
@@ -234,3 +235,9 @@ def default_solver_params(**overrides):
             raise KeyError(f"unknown LPSolver parameter {k!r}")
         setattr(p, k, v)
     return p
+
+# mi_lp_*_sparse column_filter bits (include/mi_lp.h MI_LP_COLUMNS_*).
+COLUMNS_ALL, COLUMNS_STRUCTURAL, COLUMNS_NON_BASIC = 0, 1, 2
+COLUMN_FILTERS = {"all": COLUMNS_ALL, "structural": COLUMNS_STRUCTURAL,
+                  "non_basic": COLUMNS_NON_BASIC,
+                  "structural_non_basic": COLUMNS_STRUCTURAL | COLUMNS_NON_BASIC}

@@ -116,6 +116,11 @@ def lib():
     L.mi_lp_get_dictionary.argtypes = [vp, vp, vp, vp]
     L.mi_lp_row_combinations.argtypes = [vp, vp, ctypes.c_int32, vp]
     L.mi_lp_get_tableau_rows.argtypes = [vp, vp, ctypes.c_int32, vp, vp]
+    L.mi_lp_row_combinations_sparse.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_double,
+                                                ctypes.c_uint32, vp]
+    L.mi_lp_get_tableau_rows_sparse.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_double,
+                                                ctypes.c_uint32, vp, vp]
+    L.mi_lp_get_sparse_rows.argtypes = [vp, vp, vp]
     L.mi_lp_solver_params_default.argtypes = [ctypes.POINTER(abi.MiLpSolverParams)]
     L.mi_lp_scale.argtypes = [ctypes.POINTER(abi.MiLpSolverParams), ctypes.c_int32,
                               ctypes.c_int32] + [vp] * 14
@@ -526,6 +531,48 @@ class LpHandle:
         self._call("get_tableau_rows", _p(rows), k, _p(out),
                    None if left is None else _p(left))
         return (out[:k], left[:k]) if with_left_inverses else out[:k]
+
+    def _sparse_rows(self, starts, k):
+        """The stored result of the last sparse call as (row_starts, cols, vals)."""
+        kept = int(starts[k])
+        cols = np.zeros(max(1, kept), np.int32)
+        vals = np.zeros(max(1, kept), np.float64)
+        self._call("get_sparse_rows", _p(cols), _p(vals))
+        return starts[:k + 1], cols[:kept], vals[:kept]
+
+    def row_combinations_sparse(self, Y, drop_tolerance=0.0, columns="all"):
+        """row_combinations(Y) as sparse rows, filtered and packed on the GPU:
+        (row_starts[k+1] int64, cols int32, vals float64). Row j keeps, columns
+        ascending, the columns selected by `columns` ("all", "structural",
+        "non_basic", "structural_non_basic") with |value| > drop_tolerance."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[None, :]
+        if Y.ndim != 2 or Y.shape[1] != self.lp.m:
+            raise ValueError(f"Y must be (k, {self.lp.m}), got {Y.shape}")
+        k = Y.shape[0]
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            Y = np.zeros((1, self.lp.m), np.float64)
+        starts = np.zeros(max(k, 1) + 1, np.int64)
+        self._call("row_combinations_sparse", _p(Y), k, ctypes.c_double(drop_tolerance),
+                   abi.COLUMN_FILTERS[columns], _p(starts))
+        return self._sparse_rows(starts, k)
+
+    def tableau_rows_sparse(self, rows, drop_tolerance=0.0, columns="all",
+                            with_left_inverses=False):
+        """tableau_rows(rows) as sparse rows (see row_combinations_sparse). With
+        with_left_inverses also returns the (k, m) left inverses, last."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        k = len(rows)
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            rows = np.zeros(1, np.int32)
+        starts = np.zeros(max(k, 1) + 1, np.int64)
+        left = np.zeros((max(k, 1), self.lp.m), np.float64) if with_left_inverses else None
+        self._call("get_tableau_rows_sparse", _p(rows), k, ctypes.c_double(drop_tolerance),
+                   abi.COLUMN_FILTERS[columns], _p(starts),
+                   None if left is None else _p(left))
+        out = self._sparse_rows(starts, k)
+        return out + (left[:k],) if with_left_inverses else out
 
 
 def batch_solve(handles, num_threads=4, progress=None, progress_s=15.0):
