@@ -14,7 +14,11 @@
  *
  * Preconditions are DeviceLp's own and are not checked here: filtered rows
  * ascend and are in range, column indices are in range, vectors have m (rho,
- * w, v) or N = n + m (rc, colbits, bound_diff, out) elements. */
+ * w, v, y) or N = n + m (rc, colbits, bound_diff, c, x, out) elements. The
+ * fused pricing (w given) and list_dots_over_update_row need the list's count:
+ * fetch_update_row comes first. The dual_* calls need dual_begin first;
+ * dual_take_priced_reduced_costs needs a pricing call before it, and
+ * dual_set_reduced_cost a column in [0, N). */
 #ifndef MI_LP_DEVOP_H_
 #define MI_LP_DEVOP_H_
 
@@ -78,6 +82,18 @@ typedef struct mi_devop_panel_sparse_geometry {
 /* column_dots_panel_sparse: the result needs more than `capacity` entries. */
 enum { MI_DEVOP_CAPACITY = 2 };
 
+/* DeviceLp::LastColumnDots: the last launch of the column-dot kernels. */
+typedef struct mi_devop_column_dots {
+  int32_t mode;         /* DotMode of simplex_kernels.hip: 1 pricing, 5 pricing with dots */
+  int32_t wave_per_col; /* the long-column CSC kernel (else four lanes per column) */
+  int32_t dense;        /* the dense-block kernel ran */
+  int32_t dense_unroll; /* its variant: 8, 16 or 32 (0 without a dense block) */
+} mi_devop_column_dots;
+/* DeviceLp::LastFlips: the last dual_boxed_flips. */
+typedef struct mi_devop_flips {
+  int32_t early_taken; /* it returned the flags of dual_boxed_flips_early's launch */
+} mi_devop_flips;
+
 typedef struct mi_devop_api {
   /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
   mi_devop* (*create)(int device, int m, int n, const int64_t* col_starts,
@@ -130,6 +146,24 @@ typedef struct mi_devop_api {
                                   int32_t* cols, double* vals, int64_t capacity);
   int (*last_panel_sparse)(mi_devop* h, mi_devop_panel_sparse* out);
   int (*panel_sparse_geometry)(mi_devop_panel_sparse_geometry* out);
+  /* Appended after panel_sparse_geometry. DeviceLp::Pricing: rc_out[N] =
+   * c - A^T y. With w != NULL the same pass computes a_j . w over the last
+   * update row's list: list_dots_out (N elements) receives *list_count dots
+   * in list order. w == NULL: *list_count = 0, list_dots_out is not touched. */
+  int (*pricing)(mi_devop* h, const double* c, const double* y, const double* w, double* rc_out,
+                 double* list_dots_out, int* list_count);
+  /* out[N]; only the positions of the last relevant mask are defined. */
+  int (*column_squared_norms)(mi_devop* h, double* out);
+  /* out[m]; skip_basic: the columns of the kBasic mask (set_mask which 1). */
+  int (*row_sums)(mi_devop* h, const double* x, int skip_basic, double sign, double* out);
+  /* cols == NULL: every column, flags_out holds N bytes; else n bytes. */
+  int (*dual_boxed_flips)(mi_devop* h, const int32_t* cols, int n, double threshold,
+                          uint8_t* flags_out);
+  int (*dual_boxed_flips_early)(mi_devop* h, const int32_t* cols, int n, double threshold);
+  int (*dual_take_priced_reduced_costs)(mi_devop* h);
+  int (*dual_set_reduced_cost)(mi_devop* h, int col, double value);
+  int (*last_column_dots)(mi_devop* h, mi_devop_column_dots* out);
+  int (*last_flips)(mi_devop* h, mi_devop_flips* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

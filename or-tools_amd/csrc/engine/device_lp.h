@@ -125,6 +125,16 @@ class DeviceLp : public DeviceSolver {
                std::vector<double>* list_dots = nullptr);
   // Changes whenever the device-side update-row list (and its flags) changes.
   uint64_t list_epoch() const;
+  // The last launch of the column-dot kernels (test record, set in
+  // LaunchColumnDots; with column shards: joined over the blocks of the last
+  // Pricing).
+  struct LastColumnDots {
+    int mode = -1;              // DotMode of simplex_kernels.hip
+    bool wave_per_col = false;  // the long-column CSC kernel
+    bool dense = false;         // the dense-block kernel ran
+    int dense_unroll = 0;       // its variant: 8, 16 or 32
+  };
+  LastColumnDots last_column_dots() const { return last_column_dots_; }
 
   // --- column dots of k vectors in one pass (kernels/panel_kernels.hip) ----
   // out[j * N + col] = a_col . y_j (ColumnScalarProduct's order, sparse.h:
@@ -228,6 +238,12 @@ class DeviceLp : public DeviceSolver {
   // threshold, no reduced cost was written since and none of those columns'
   // bits changed; otherwise it decides as usual. MILP_EARLY_FLIPS=0: off.
   void DualBoxedFlipsEarly(const std::vector<int>& cols, double threshold);
+  // Whether the last DualBoxedFlips returned the early launch's flags (test
+  // record).
+  struct LastFlips {
+    bool early_taken = false;
+  };
+  LastFlips last_flips() const { return last_flips_; }
 
   // --- dense triangular solves of the LU (device_solve.hip) -------------
   struct TriBuffer {  // a device buffer of the triangular-solve state
@@ -670,6 +686,8 @@ class DeviceLp : public DeviceSolver {
   bool list_mirror_ = true;
   bool mapped_result_ = false;  // the last Compact wrote to h_map_
   LastPaths paths_;
+  LastColumnDots last_column_dots_;
+  LastFlips last_flips_;
   void RowPath(int path) {  // a new update row: its compaction (if any) follows
     paths_.update_row = path;
     paths_.compact = kCompactNone;

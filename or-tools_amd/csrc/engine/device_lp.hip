@@ -986,6 +986,10 @@ void DeviceLp::LaunchColumnDots(int mode, const double* d_y, const double* d_c,
   const double sparse_avg =
       (nd_ > 0 ? (ns_ > 0 ? double(sparse_entries_) / ns_ : 0.0) : avg_col_len_);
   a.drop_tolerance = drop_;
+  last_column_dots_.mode = mode;
+  last_column_dots_.wave_per_col = sparse_avg >= 32.0;
+  last_column_dots_.dense = nd_ > 0;
+  last_column_dots_.dense_unroll = nd_ > 0 ? dense_unroll_ : 0;
   Check(milp_launch::column_dot(mode, sparse_avg >= 32.0, a, S(stream_)), "column dots");
   if (nd_ > 0) {
     milp_kernels::DenseArgs d{};
@@ -2236,6 +2240,7 @@ void DeviceLp::DualUpdateReducedCosts(double mult, int leaving_col, double leavi
 
 void DeviceLp::DualBoxedFlips(const std::vector<int>* cols, double threshold,
                               std::vector<uint8_t>* flags) {
+  last_flips_.early_taken = false;
   if (!shards_.empty()) return ShardedDualBoxedFlips(cols, threshold, flags);
   CallTimer timer(&stats_, MI_K_DUAL_RATIO);
   const int n = cols != nullptr ? static_cast<int>(cols->size()) : n_total_;
@@ -2250,6 +2255,7 @@ void DeviceLp::DualBoxedFlips(const std::vector<int>* cols, double threshold,
     }
     WaitEarlyFlips();  // its buffers are reused below either way
     if (same) {
+      last_flips_.early_taken = true;
       std::memcpy(flags->data(), h_flip_flags_, n);
       return;
     }

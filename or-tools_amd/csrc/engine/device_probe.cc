@@ -280,6 +280,86 @@ int PanelSparseGeometry(mi_devop_panel_sparse_geometry* out) {
   return 0;
 }
 
+int Pricing(mi_devop* h, const double* c, const double* y, const double* w, double* rc_out,
+            double* list_dots_out, int* list_count) {
+  return Guard(h, [&] {
+    const int m = h->csc.num_rows();
+    const int n = h->csc.num_cols();
+    const std::vector<double> cv(c, c + n);
+    const std::vector<double> yv(y, y + m);
+    std::vector<double> rc, dots;
+    *list_count = 0;
+    if (w != nullptr) {
+      const std::vector<double> wv(w, w + m);
+      h->dev.Pricing(cv, yv, &rc, &wv, &dots);
+      *list_count = static_cast<int>(dots.size());
+      if (!dots.empty()) std::memcpy(list_dots_out, dots.data(), dots.size() * sizeof(double));
+    } else {
+      h->dev.Pricing(cv, yv, &rc);
+    }
+    if (!rc.empty()) std::memcpy(rc_out, rc.data(), rc.size() * sizeof(double));
+  });
+}
+
+int ColumnSquaredNorms(mi_devop* h, double* out) {
+  return Guard(h, [&] {
+    std::vector<double> v;
+    h->dev.ColumnSquaredNorms(&v);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(double));
+  });
+}
+
+int RowSums(mi_devop* h, const double* x, int skip_basic, double sign, double* out) {
+  return Guard(h, [&] {
+    const std::vector<double> xv(x, x + h->csc.num_cols());
+    std::vector<double> v;
+    h->dev.RowSums(xv, skip_basic != 0, sign, &v);
+    if (!v.empty()) std::memcpy(out, v.data(), v.size() * sizeof(double));
+  });
+}
+
+int DualBoxedFlips(mi_devop* h, const int32_t* cols, int n, double threshold,
+                   uint8_t* flags_out) {
+  return Guard(h, [&] {
+    std::vector<uint8_t> flags;
+    if (cols != nullptr) {
+      const std::vector<int> c(cols, cols + n);
+      h->dev.DualBoxedFlips(&c, threshold, &flags);
+    } else {
+      h->dev.DualBoxedFlips(nullptr, threshold, &flags);
+    }
+    if (!flags.empty()) std::memcpy(flags_out, flags.data(), flags.size());
+  });
+}
+
+int DualBoxedFlipsEarly(mi_devop* h, const int32_t* cols, int n, double threshold) {
+  return Guard(h, [&] {
+    h->dev.DualBoxedFlipsEarly(std::vector<int>(cols, cols + n), threshold);
+  });
+}
+
+int DualTakePricedReducedCosts(mi_devop* h) {
+  return Guard(h, [&] { h->dev.DualTakePricedReducedCosts(); });
+}
+
+int DualSetReducedCost(mi_devop* h, int col, double value) {
+  return Guard(h, [&] { h->dev.DualSetReducedCost(col, value); });
+}
+
+int LastColumnDots(mi_devop* h, mi_devop_column_dots* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastColumnDots p = h->dev.last_column_dots();
+    out->mode = p.mode;
+    out->wave_per_col = p.wave_per_col ? 1 : 0;
+    out->dense = p.dense ? 1 : 0;
+    out->dense_unroll = p.dense_unroll;
+  });
+}
+
+int LastFlips(mi_devop* h, mi_devop_flips* out) {
+  return Guard(h, [&] { out->early_taken = h->dev.last_flips().early_taken ? 1 : 0; });
+}
+
 static_assert(int{MI_DEVOP_PANEL_LONG_COLUMNS} == int{milp::DeviceLp::kPanelLongColumns},
               "mi_lp_devop.h restates DeviceLp's panel shapes");
 static_assert(int{MI_DEVOP_ROW_COLUMN_WISE_GENERAL} == int{milp::DeviceLp::kRowColumnWiseGeneral} &&
@@ -305,4 +385,9 @@ extern "C" const mi_devop_api mi_devop_table = {
     TakeKernelMs,
     ColumnDotsPanelSparse, LastPanelSparse,
     PanelSparseGeometry,
+    Pricing,          ColumnSquaredNorms,
+    RowSums,          DualBoxedFlips,
+    DualBoxedFlipsEarly, DualTakePricedReducedCosts,
+    DualSetReducedCost, LastColumnDots,
+    LastFlips,
 };

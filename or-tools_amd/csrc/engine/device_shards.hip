@@ -386,6 +386,7 @@ void DeviceLp::ShardedPricing(const std::vector<double>& c, const std::vector<do
   const int ns = num_shards();
   std::vector<std::string> parts(ns);
   std::vector<double> cs, part, dots;
+  last_column_dots_ = LastColumnDots();
   for (int s = 0; s < ns; ++s) {
     if (!IsLocalShard(s)) continue;
     DeviceLp& d = Shard(s);
@@ -395,6 +396,11 @@ void DeviceLp::ShardedPricing(const std::vector<double>& c, const std::vector<do
       const int b = shard_begin_[s];
       cs.assign(c.begin() + b, c.begin() + shard_begin_[s + 1]);
       d.Pricing(cs, y, &part, w, w != nullptr ? &dots : nullptr);
+      const LastColumnDots p = d.last_column_dots();
+      last_column_dots_.mode = p.mode;
+      last_column_dots_.wave_per_col = last_column_dots_.wave_per_col || p.wave_per_col;
+      last_column_dots_.dense = last_column_dots_.dense || p.dense;
+      last_column_dots_.dense_unroll = std::max(last_column_dots_.dense_unroll, p.dense_unroll);
     }
     PartWriter pw;
     pw.Put(part);

@@ -2,14 +2,17 @@
 
 TEST INFRASTRUCTURE ONLY. Pure Python/numpy, no C: it cannot share a mistake
 with the engine. RefState holds what the device holds between operations: the
-coefficient array, the last list, rc / colbits / bound_diff and the relevant
-mask. Every product is one IEEE double multiplication and every sum one IEEE
-addition in the order the operation defines (numpy element-wise arithmetic
-does not fuse), so results are compared with the device on bit patterns.
+coefficient array, the last list, rc / colbits / bound_diff, the relevant mask
+and the last pricing result. Every product is one IEEE double multiplication
+and every sum one IEEE addition in the order the operation defines (numpy
+element-wise arithmetic does not fuse), so results are compared with the
+device on bit patterns.
 """
 import numpy as np
 
 COL_CAN_DECREASE, COL_CAN_INCREASE, COL_BOXED = 1, 2, 4
+# glop::VariableStatus in bits 3-5 of a column's byte (lp_types.h:188-219).
+STATUS_SHIFT, STATUS_AT_LOWER, STATUS_AT_UPPER = 3, 2, 3
 
 
 def bits(a):
@@ -137,6 +140,57 @@ class RefState:
     def list_dots(self, cols, v):
         return column_scalar_products(self.mat, cols, v)
 
+    # --- pricing, row sums, norms -------------------------------------------
+    def pricing(self, c, y):
+        """rc[j] = c[j] - a_j . y for every column of [A | I]
+        (reduced_costs.cc:372-381); kept for take_priced(), the dots as
+        priced_dots."""
+        dots = column_scalar_products(self.mat, np.arange(self.mat.N), y)
+        self.priced_dots = dots
+        self.priced = np.asarray(c, np.float64) - dots
+        return self.priced.copy()
+
+    def pricing_with_dots(self, c, y, w):
+        """(rc, a_j . w over the last update row's list, in list order)."""
+        return self.pricing(c, y), column_scalar_products(self.mat, self.list, w)
+
+    def row_sums(self, x, skip, sign):
+        """Per row: +0.0, then (sign * x_j) * a_rj added in increasing column
+        order. An entry is left out when skip[j] is set or its multiplier
+        sign * x_j == 0.0 (+-0.0; a NaN multiplier compares unequal and stays)
+        (variable_values.cc:101-131, sparse.h:393)."""
+        mat = self.mat
+        x = np.asarray(x, np.float64)
+        skip = np.zeros(mat.N, bool) if skip is None else np.asarray(skip, bool)
+        out = np.zeros(mat.m)
+        for r in range(mat.m):
+            cols = mat.t_cols[r]
+            mult = sign * x[cols]
+            live = ~skip[cols] & (mult != 0.0)
+            acc = np.float64(0.0)
+            for p in (mult[live] * mat.t_vals[r][live]):
+                acc = acc + p
+            out[r] = acc
+        return out
+
+    def column_squared_norms(self):
+        """1.0 + (v_0 v_0 + v_1 v_1 + ... in entry order, from +0.0) at the
+        relevant columns (primal_edge_norms.cc:153-158 with an identity
+        basis); NaN marks the other positions, which are undefined."""
+        mat = self.mat
+        out = np.full(mat.N, np.nan)
+        rel = np.nonzero(self.relevant)[0]
+        lens = mat.col_len[rel]
+        for L in np.unique(lens):
+            sel = rel[lens == L]
+            v = mat.c_vals[mat.starts[sel][:, None] + np.arange(L)[None, :]]
+            sq = v * v
+            acc = np.zeros(len(sel))
+            for t in range(L):
+                acc = acc + sq[:, t]
+            out[sel] = 1.0 + acc
+        return out
+
     # --- dual device mode ---------------------------------------------------
     def dual_begin(self, rc, colbits, bound_diff):
         self.rc = np.asarray(rc, np.float64).copy()
@@ -200,6 +254,32 @@ class RefState:
                     best_coeff, entering = mag, s
             popped.append(s)
         return B, kept, np.array(sorted(popped), dtype=np.int64), entering
+
+    def boxed_flips(self, cols, threshold):
+        """boxed_flips_kernel (revised_simplex.cc:2391-2437): with status =
+        (bits >> 3) & 7, a column flips when it sits at its upper bound
+        (status 3) with rc > threshold, or at its lower bound (status 2) with
+        rc < -threshold. cols None: all N columns, and only those with
+        COL_BOXED set can flip; with a list the bit is not consulted. uint8
+        flags, one per column (or list slot)."""
+        if cols is None:
+            col = np.arange(self.mat.N)
+            allowed = (self.colbits & COL_BOXED) != 0
+        else:
+            col = np.asarray(cols, np.int64)
+            allowed = np.ones(len(col), bool)
+        rc = self.rc[col]
+        status = (self.colbits[col] >> STATUS_SHIFT) & 7
+        flip = ((rc > threshold) & (status == STATUS_AT_UPPER)) | \
+               ((rc < -threshold) & (status == STATUS_AT_LOWER))
+        return (allowed & flip).astype(np.uint8)
+
+    def take_priced(self):
+        """The last pricing() result becomes the reduced costs."""
+        self.rc = self.priced.copy()
+
+    def set_reduced_cost(self, col, value):
+        self.rc[col] = value
 
     def update_reduced_costs(self, mult, leaving_col, leaving_value, entering_col):
         """rc[list[i]] += mult * coeff[i] except the entering column; then

@@ -9,34 +9,7 @@ import pytest
 import device_cases as dc
 from device_ref import (COL_BOXED, COL_CAN_DECREASE, COL_CAN_INCREASE, Matrix, RefState, bits,
                         column_scalar_products)
-
-
-def _exact(x):
-    """A double as (integer, e) with x = integer / 2**e."""
-    n, d = float(x).as_integer_ratio()
-    return n, d.bit_length() - 1
-
-
-def _within_gamma(value, terms):
-    """|value - sum of the exact products| <= gamma_k * sum |product| with
-    gamma_k = k u / (1 - k u), u = 2^-53: the bound of a k-term dot product
-    summed in any order (Higham, Accuracy and Stability, 3.1). The table's
-    -0.0 case multiplies 1e-200 by -1e-200, which underflows, so the model
-    with underflow applies: fl(a b) = a b (1 + d) + e with |e| <= 2^-1075
-    (half the smallest subnormal; additions do not underflow), which adds
-    k 2^-1075 / (1 - k u) to the bound -- nothing at the scale of any other
-    value here. Integers only."""
-    k = len(terms)
-    prods = []
-    for a, b in terms:
-        (na, ea), (nb, eb) = _exact(a), _exact(b)
-        prods.append((na * nb, ea + eb))
-    vn, ve = _exact(value)
-    E = max([e for _, e in prods] + [ve, 1075])
-    s = sum(n << (E - e) for n, e in prods)
-    mag = sum(abs(n) << (E - e) for n, e in prods)
-    err = abs((vn << (E - ve)) - s)
-    return err * ((1 << 53) - k) <= k * mag + k * (1 << (E - 1075 + 53))
+from exact_bound import within_gamma as _within_gamma
 
 
 def _row_terms(mat, rows, rho, alg):
