@@ -329,6 +329,42 @@ int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
                                   int64_t* row_starts, double* left_inverses);
 int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals);
 
+/* The other half: the row sums [A | I] x_j of k candidate points in one call
+ * that reads A once per panel of up to 16 points (what a caller reads cut
+ * violations and row feasibility of roundings, neighbours or ray combinations
+ * off, before it pays for mi_lp_batch_solve_bounds). Each sum is Glop's
+ * row-activity sum (variable_values.cc:101-131 through
+ * ColumnAddMultipleToDenseColumn, sparse.h:389-399):
+ *   mi_lp_column_combinations            out[j m + r] starts from +0.0 and takes the
+ *                                        entries (col, a) of row r of [A | I] in
+ *                                        increasing column order: an entry is skipped when
+ *                                        x_j[col] == 0.0 (+0.0 and -0.0; a NaN compares
+ *                                        unequal and is not skipped), otherwise
+ *                                        acc = acc + x_j[col] * a, every product and every
+ *                                        sum rounded separately (no FMA). A row whose live
+ *                                        multipliers are all zero gives +0.0. No mask, no
+ *                                        sign, no tolerance. Changes no state a later
+ *                                        solve reads.
+ *   mi_lp_column_combinations_from       the same for the points x_j = base with
+ *                                        x_j[cols[i]] = vals[i] for i in
+ *                                        [starts[j], starts[j+1]), built on the GPU: only
+ *                                        base and the override lists go up. Bit for bit
+ *                                        the dense call on the materialised points; an
+ *                                        override to +-0.0 skips the entry, NaN and +-inf
+ *                                        propagate.
+ * x: k x (n+m), vector-major, structural columns then slack columns. base:
+ * n+m. out: k x m, vector-major. starts: k+1 entries with starts[0] == 0;
+ * cols and vals may be NULL when starts[k] == 0. k = 0 writes nothing and
+ * succeeds. MI_LP_ERROR_INVALID_PROBLEM with nothing written: k < 0,
+ * starts[0] != 0 or starts decreasing, a column outside [0, n+m), the same
+ * column twice within one point. NULL h, x, base, starts or out, or NULL cols
+ * or vals with starts[k] > 0: MI_LP_ERROR_NULL. Before a solve:
+ * MI_LP_ERROR_STATE. Other errors as mi_lp_row_combinations. */
+int mi_lp_column_combinations(mi_lp* h, const double* x, int32_t k, double* out);
+int mi_lp_column_combinations_from(mi_lp* h, const double* base, int32_t k,
+                                   const int64_t* starts, const int32_t* cols,
+                                   const double* vals, double* out);
+
 /* interrupt may be NULL; a non-zero value stops the solve like a time limit
  * (glop_interface.cc:138-140). */
 int mi_lp_solve(mi_lp* h, const volatile int32_t* interrupt, mi_lp_result* out);

@@ -94,6 +94,21 @@ typedef struct mi_devop_flips {
   int32_t early_taken; /* it returned the flags of dual_boxed_flips_early's launch */
 } mi_devop_flips;
 
+/* DeviceLp::LastRowPanel: the last row_sums_panel / row_sums_panel_from. */
+enum { MI_DEVOP_ROW_PANEL_NONE = 0, MI_DEVOP_ROW_PANEL_DIRECT = 1 };
+typedef struct mi_devop_row_panel {
+  int32_t panels;             /* panels of up to 16 points */
+  int32_t width;              /* padded width of the last panel: 1, 4 or 16 */
+  int32_t kernel;             /* MI_DEVOP_ROW_PANEL_* of the last panel */
+  int32_t reserved;
+  int64_t overrides_up_bytes; /* host-to-device bytes of a row_sums_panel_from call */
+} mi_devop_row_panel;
+/* row_sums_panel_kernel's shape (kernels/kernel_args.h). */
+typedef struct mi_devop_row_panel_geometry {
+  int32_t rows_per_workgroup[3]; /* at widths 1, 4 and 16 */
+  int32_t chunk;                 /* staging chunk length; 0: the kernel does not stage */
+} mi_devop_row_panel_geometry;
+
 typedef struct mi_devop_api {
   /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
   mi_devop* (*create)(int device, int m, int n, const int64_t* col_starts,
@@ -164,6 +179,17 @@ typedef struct mi_devop_api {
   int (*dual_set_reduced_cost)(mi_devop* h, int col, double value);
   int (*last_column_dots)(mi_devop* h, mi_devop_column_dots* out);
   int (*last_flips)(mi_devop* h, mi_devop_flips* out);
+  /* Appended after last_flips. x: k x N, out: k x m, both vector-major
+   * (DeviceLp::RowSumsPanel). */
+  int (*row_sums_panel)(mi_devop* h, const double* x, int k, double* out);
+  /* base: N; starts: k + 1; cols / vals: starts[k] entries, NULL when that is
+   * 0 (DeviceLp::RowSumsPanelFrom). Checked here, since a bad column would be
+   * a store out of bounds: starts[0] == 0, starts non-decreasing, columns in
+   * [0, N), no column twice within a point. */
+  int (*row_sums_panel_from)(mi_devop* h, const double* base, int k, const int64_t* starts,
+                             const int32_t* cols, const double* vals, double* out);
+  int (*last_row_panel)(mi_devop* h, mi_devop_row_panel* out);
+  int (*row_panel_geometry)(mi_devop_row_panel_geometry* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

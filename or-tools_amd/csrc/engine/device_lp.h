@@ -204,6 +204,43 @@ class DeviceLp : public DeviceSolver {
   void RowSums(const std::vector<double>& x, bool skip_basic, double sign,
                std::vector<double>* out);
 
+  // --- row sums of k points in one pass (kernels/panel_kernels.hip) -----
+  // out[j * m + r] = RowSums(x_j, false, 1.0)[r] bit for bit, for j < k: from
+  // +0.0, row r's entries in increasing column order, acc = acc + x_j[col] * a,
+  // entries with x_j[col] == +-0.0 left out. x is k x N and out k x m, both
+  // vector-major on the host. The points go up vector-major in panels of up
+  // to 16 (widths 1, 4 and 16, padded with zero points whose results are not
+  // stored) and are interleaved on the device; the CSR of [A | I] is read
+  // once per panel. Uses ColumnDotsPanel's buffers with the roles swapped
+  // (d_panel_i_: the interleaved points, d_panel_y_: the interleaved
+  // results, d_panel_out_: vector-major staging of both) and, like it, writes
+  // nothing a solve reads and has no id in mi_lp_kernel_stats; its kernel
+  // time is in TakePanelKernelMs. With column shards it stays on the unsplit
+  // handle, as RowSums does. Synchronizes before it returns.
+  void RowSumsPanel(const double* x, int k, double* out);
+  // The same for the points x_j = base (N values) with x_j[cols[i]] = vals[i]
+  // for i in [starts[j], starts[j + 1]), built on the device: base, starts,
+  // cols and vals go up once per call (8 N + 12 overrides + 8 (k + 1) bytes).
+  // Preconditions (ValidOverrides): starts[0] == 0, starts non-decreasing,
+  // columns in [0, N), no column twice within a point. cols / vals may be
+  // null when starts[k] == 0.
+  void RowSumsPanelFrom(const double* base, int k, const int64_t* starts, const int32_t* cols,
+                        const double* vals, double* out);
+  // Linear in k + overrides (one stamp per column).
+  static bool ValidOverrides(int num_cols, int k, const int64_t* starts, const int32_t* cols);
+  // The last RowSumsPanel / RowSumsPanelFrom (test record).
+  enum RowPanelKernel { kRowPanelNone = 0, kRowPanelDirect = 1 };
+  struct LastRowPanel {
+    int panels = 0;
+    int width = 0;                   // of the last panel
+    int kernel = kRowPanelNone;      // path of the last panel
+    int64_t overrides_up_bytes = 0;  // host-to-device bytes of a RowSumsPanelFrom call
+  };
+  LastRowPanel last_row_panel() const { return last_row_panel_; }
+  // Rows per workgroup of row_sums_panel_kernel at widths 1, 4 and 16, and
+  // its staging chunk length (0: it reads the rows directly), for the tests.
+  static void RowPanelGeometry(int rows_per_workgroup[3], int* chunk);
+
   // --- dual device mode: device-resident reduced costs ------------------
   // (see simplex.cc RevisedSimplex::DualDeviceMode). colbits: one byte per
   // column (kernel_args.h kCol*), bound_diff: upper - lower per column.
@@ -470,6 +507,17 @@ class DeviceLp : public DeviceSolver {
   size_t panel_cols_cap_ = 0, panel_mask_cap_ = 0, panel_counts_cap_ = 0,
          panel_offsets_cap_ = 0;  // bytes
   LastPanelSparse last_panel_sparse_;
+  // RowSumsPanel's additions, kept like the buffers above.
+  void RowPanelReserveOverrides(int k, int64_t overrides);
+  void RowPanelSums(int first, int kp, int width, double* out);
+  void PanelAddKernelMs();
+  double* d_panel_base_ = nullptr;          // the base point, N
+  int64_t* d_panel_ov_starts_ = nullptr;    // k + 1
+  int32_t* d_panel_ov_cols_ = nullptr;      // overrides of the whole call
+  double* d_panel_ov_vals_ = nullptr;
+  size_t panel_base_cap_ = 0, panel_ov_starts_cap_ = 0, panel_ov_cols_cap_ = 0,
+         panel_ov_vals_cap_ = 0;  // bytes
+  LastRowPanel last_row_panel_;
   bool panel_timing_ = false;
   double panel_kernel_ms_ = 0.0;
   void* ev_panel_[2] = {nullptr, nullptr};

@@ -1663,6 +1663,14 @@ void DeviceLp::FreePanelBuffers() {
   d_panel_counts_ = nullptr;
   d_panel_offsets_ = h_panel_totals_ = nullptr;
   panel_cols_cap_ = panel_mask_cap_ = panel_counts_cap_ = panel_offsets_cap_ = 0;
+  if (d_panel_base_) (void)hipFree(d_panel_base_);
+  if (d_panel_ov_starts_) (void)hipFree(d_panel_ov_starts_);
+  if (d_panel_ov_cols_) (void)hipFree(d_panel_ov_cols_);
+  if (d_panel_ov_vals_) (void)hipFree(d_panel_ov_vals_);
+  d_panel_base_ = d_panel_ov_vals_ = nullptr;
+  d_panel_ov_starts_ = nullptr;
+  d_panel_ov_cols_ = nullptr;
+  panel_base_cap_ = panel_ov_starts_cap_ = panel_ov_cols_cap_ = panel_ov_vals_cap_ = 0;
   for (void*& e : ev_panel_) {
     if (e) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(e));
     e = nullptr;
@@ -1765,7 +1773,7 @@ void DeviceLp::PanelKernelsLaunched() {
 }
 
 // After that download: the kernel time and the record of the panel.
-void DeviceLp::PanelDone(const PanelPlan& plan, int width, LastPanel* record) {
+void DeviceLp::PanelAddKernelMs() {
   if (panel_timing_) {
     float ms = 0.0f;
     Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(ev_panel_[0]),
@@ -1773,6 +1781,10 @@ void DeviceLp::PanelDone(const PanelPlan& plan, int width, LastPanel* record) {
           "ev time");
     panel_kernel_ms_ += ms;
   }
+}
+
+void DeviceLp::PanelDone(const PanelPlan& plan, int width, LastPanel* record) {
+  PanelAddKernelMs();
   record->sparse = plan.sparse_cols > 0
                        ? (plan.long_columns ? kPanelLongColumns : kPanelShortColumns)
                        : kPanelNone;
@@ -1895,6 +1907,131 @@ void DeviceLp::ColumnDotsPanelSparse(const double* y, int k, double drop_toleran
     last_panel_sparse_.bytes_down += int64_t(kp) * 8 + kept * 12;
   }
   DeviceOp("column dots panel sparse done");
+}
+
+void DeviceLp::RowPanelGeometry(int rows_per_workgroup[3], int* chunk) {
+  rows_per_workgroup[0] = milp_kernels::kRowPanelThreads;
+  rows_per_workgroup[1] = milp_kernels::kRowPanelThreads / 4;
+  rows_per_workgroup[2] = milp_kernels::kRowPanelThreads / 16;
+  *chunk = milp_kernels::kRowPanelChunk;
+}
+
+bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const int32_t* cols) {
+  if (k < 0 || starts[0] != 0) return false;
+  for (int j = 0; j < k; ++j) {
+    if (starts[j + 1] < starts[j]) return false;
+  }
+  if (starts[k] == 0) return true;
+  if (cols == nullptr) return false;
+  std::vector<int32_t> stamp(size_t(std::max(num_cols, 0)), 0);  // point + 1 that last set it
+  for (int j = 0; j < k; ++j) {
+    for (int64_t i = starts[j]; i < starts[j + 1]; ++i) {
+      const int32_t c = cols[i];
+      if (c < 0 || c >= num_cols || stamp[c] == j + 1) return false;
+      stamp[c] = j + 1;
+    }
+  }
+  return true;
+}
+
+// The interleaved points of one panel are in d_panel_i_: the sums into
+// d_panel_y_, vector-major into d_panel_out_, down to out, and the record.
+void DeviceLp::RowPanelSums(int first, int kp, int width, double* out) {
+  milp_kernels::RowPanelArgs a{};
+  a.t_starts = d_t_starts_;
+  a.t_cols = d_t_cols_;
+  a.t_vals = d_t_vals_;
+  a.x = d_panel_i_;
+  a.num_rows = m_;
+  a.kp = kp;
+  a.out = d_panel_y_;
+  Check(milp_launch::row_sums_panel(width, a, S(stream_)), "row sums panel");
+  Check(milp_launch::panel_deinterleave(width, d_panel_y_, m_, kp, d_panel_out_, m_, S(stream_)),
+        "row panel de-interleave");
+  PanelKernelsLaunched();
+  Download(out + size_t(first) * m_, d_panel_out_, size_t(kp) * m_ * sizeof(double));
+  PanelAddKernelMs();
+  last_row_panel_.panels += 1;
+  last_row_panel_.width = width;
+  last_row_panel_.kernel = kRowPanelDirect;
+}
+
+void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
+  last_row_panel_ = LastRowPanel();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("row sums panel");
+  (void)PanelBegin();  // the timing events
+  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
+    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
+    const int width = PanelWidth(kp);
+    PanelReserve(width, kp);
+    Upload(d_panel_out_, x + size_t(first) * n_total_, size_t(kp) * n_total_ * sizeof(double));
+    if (panel_timing_) {
+      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
+    }
+    Check(milp_launch::panel_interleave(width, d_panel_out_, n_total_, n_total_, kp, d_panel_i_,
+                                        S(stream_)),
+          "row panel interleave");
+    RowPanelSums(first, kp, width, out);
+  }
+  DeviceOp("row sums panel done");
+}
+
+// Grows the override call's own buffers: the base point and the call's
+// starts, columns and values.
+void DeviceLp::RowPanelReserveOverrides(int k, int64_t overrides) {
+  const auto grow = [this](void** p, size_t* cap, size_t bytes, const char* what) {
+    if (bytes <= *cap) return;
+    if (*p) Check(hipFree(*p), what);
+    *p = nullptr;
+    *cap = 0;
+    Check(hipMalloc(p, bytes), what);
+    *cap = bytes;
+  };
+  grow(reinterpret_cast<void**>(&d_panel_base_), &panel_base_cap_,
+       size_t(n_total_) * sizeof(double), "panel base point");
+  grow(reinterpret_cast<void**>(&d_panel_ov_starts_), &panel_ov_starts_cap_,
+       (size_t(k) + 1) * sizeof(int64_t), "panel override starts");
+  grow(reinterpret_cast<void**>(&d_panel_ov_cols_), &panel_ov_cols_cap_,
+       size_t(overrides) * sizeof(int32_t), "panel override columns");
+  grow(reinterpret_cast<void**>(&d_panel_ov_vals_), &panel_ov_vals_cap_,
+       size_t(overrides) * sizeof(double), "panel override values");
+}
+
+void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts,
+                                const int32_t* cols, const double* vals, double* out) {
+  last_row_panel_ = LastRowPanel();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("row sums panel from");
+  (void)PanelBegin();  // the timing events
+  const int64_t overrides = starts[k];
+  RowPanelReserveOverrides(k, overrides);
+  Upload(d_panel_base_, base, size_t(n_total_) * sizeof(double));
+  Upload(d_panel_ov_starts_, starts, (size_t(k) + 1) * sizeof(int64_t));
+  Upload(d_panel_ov_cols_, cols, size_t(overrides) * sizeof(int32_t));
+  Upload(d_panel_ov_vals_, vals, size_t(overrides) * sizeof(double));
+  last_row_panel_.overrides_up_bytes =
+      8 * int64_t(n_total_) + 12 * overrides + 8 * (int64_t(k) + 1);
+  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
+    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
+    const int width = PanelWidth(kp);
+    PanelReserve(width, kp);
+    if (panel_timing_) {
+      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
+    }
+    Check(milp_launch::panel_fill(width, d_panel_base_, n_total_, kp, d_panel_i_, S(stream_)),
+          "row panel fill");
+    milp_kernels::RowPanelOverrideArgs o{};
+    o.starts = d_panel_ov_starts_ + first;
+    o.cols = d_panel_ov_cols_;
+    o.vals = d_panel_ov_vals_;
+    o.kp = kp;
+    o.x = d_panel_i_;
+    Check(milp_launch::panel_override(width, o, starts[first + kp] - starts[first], S(stream_)),
+          "row panel overrides");
+    RowPanelSums(first, kp, width, out);
+  }
+  DeviceOp("row sums panel from done");
 }
 
 void DeviceLp::ColumnSquaredNorms(std::vector<double>* out) {

@@ -360,6 +360,39 @@ int LastFlips(mi_devop* h, mi_devop_flips* out) {
   return Guard(h, [&] { out->early_taken = h->dev.last_flips().early_taken ? 1 : 0; });
 }
 
+int RowSumsPanel(mi_devop* h, const double* x, int k, double* out) {
+  return Guard(h, [&] { h->dev.RowSumsPanel(x, k, out); });
+}
+
+int RowSumsPanelFrom(mi_devop* h, const double* base, int k, const int64_t* starts,
+                     const int32_t* cols, const double* vals, double* out) {
+  return Guard(h, [&] {
+    if (!milp::DeviceLp::ValidOverrides(h->csc.num_cols(), k, starts, cols) ||
+        (starts[k] > 0 && vals == nullptr)) {
+      throw milp::DeviceError("row_sums_panel_from: bad overrides");
+    }
+    h->dev.RowSumsPanelFrom(base, k, starts, cols, vals, out);
+  });
+}
+
+int LastRowPanel(mi_devop* h, mi_devop_row_panel* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastRowPanel p = h->dev.last_row_panel();
+    out->panels = p.panels;
+    out->width = p.width;
+    out->kernel = p.kernel;
+    out->reserved = 0;
+    out->overrides_up_bytes = p.overrides_up_bytes;
+  });
+}
+
+int RowPanelGeometry(mi_devop_row_panel_geometry* out) {
+  milp::DeviceLp::RowPanelGeometry(out->rows_per_workgroup, &out->chunk);
+  return 0;
+}
+
+static_assert(int{MI_DEVOP_ROW_PANEL_DIRECT} == int{milp::DeviceLp::kRowPanelDirect},
+              "mi_lp_devop.h restates DeviceLp's row panel paths");
 static_assert(int{MI_DEVOP_PANEL_LONG_COLUMNS} == int{milp::DeviceLp::kPanelLongColumns},
               "mi_lp_devop.h restates DeviceLp's panel shapes");
 static_assert(int{MI_DEVOP_ROW_COLUMN_WISE_GENERAL} == int{milp::DeviceLp::kRowColumnWiseGeneral} &&
@@ -390,4 +423,6 @@ extern "C" const mi_devop_api mi_devop_table = {
     DualBoxedFlipsEarly, DualTakePricedReducedCosts,
     DualSetReducedCost, LastColumnDots,
     LastFlips,
+    RowSumsPanel,     RowSumsPanelFrom,
+    LastRowPanel,     RowPanelGeometry,
 };

@@ -6374,6 +6374,56 @@ int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
   return MI_LP_OK;
 }
 
+int mi_lp_column_combinations(mi_lp* h, const double* x, int32_t k, double* out) {
+  if (h == nullptr || x == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  try {
+    (void)hipSetDevice(h->device);
+    h->simplex.device().RowSumsPanel(x, k, out);
+  } catch (const milp::DeviceError& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+  return MI_LP_OK;
+}
+
+int mi_lp_column_combinations_from(mi_lp* h, const double* base, int32_t k,
+                                   const int64_t* starts, const int32_t* cols,
+                                   const double* vals, double* out) {
+  if (h == nullptr || base == nullptr || starts == nullptr || out == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  try {
+    // starts first: starts[k] is read only once the entries before it are
+    // known to ascend from 0.
+    if (starts[0] != 0) return MI_LP_ERROR_INVALID_PROBLEM;
+    for (int32_t j = 0; j < k; ++j) {
+      if (starts[j + 1] < starts[j]) return MI_LP_ERROR_INVALID_PROBLEM;
+    }
+    if (starts[k] > 0 && (cols == nullptr || vals == nullptr)) return MI_LP_ERROR_NULL;
+    if (!milp::DeviceLp::ValidOverrides(h->lp.n + h->lp.m, k, starts, cols)) {
+      return MI_LP_ERROR_INVALID_PROBLEM;
+    }
+    (void)hipSetDevice(h->device);
+    h->simplex.device().RowSumsPanelFrom(base, k, starts, cols, vals, out);
+  } catch (const milp::DeviceError& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+  return MI_LP_OK;
+}
+
 int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals) {
   if (h == nullptr || cols == nullptr || vals == nullptr) return MI_LP_ERROR_NULL;
   if (!h->sparse_rows_stored) return MI_LP_ERROR_STATE;

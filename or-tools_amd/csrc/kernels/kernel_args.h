@@ -96,6 +96,34 @@ struct PanelSparseArgs {
   double* vals;
 };
 
+// Row sums of [A | I] against a panel of K points (panel_kernels.hip,
+// row_sums_panel). The points are column-interleaved, x[col * K + v], zero
+// for the padding points v >= kp; the results are row-interleaved,
+// out[row * K + v], written for v < kp. A 256-thread workgroup owns 256 / K
+// rows; the kernel reads the rows' entries directly (no LDS staging).
+constexpr int kRowPanelThreads = 256;
+constexpr int kRowPanelUnroll = 8;  // x gathers in flight ahead of the ordered adds
+constexpr int kRowPanelChunk = 0;   // staging chunk length; 0: the kernel does not stage
+struct RowPanelArgs {
+  const int64_t* t_starts;  // CSR of [A | I]
+  const int32_t* t_cols;
+  const double* t_vals;
+  const double* x;
+  int num_rows;
+  int kp;  // points in use (<= K)
+  double* out;
+};
+// The overrides of one panel scattered into the interleaved points:
+// x[cols[i] * K + v] = vals[i] for i in [starts[v], starts[v + 1]), v < kp.
+// No column repeats within a point, so no two stores meet.
+struct RowPanelOverrideArgs {
+  const int64_t* starts;  // kp + 1 entries, positions into cols / vals
+  const int32_t* cols;
+  const double* vals;
+  int kp;
+  double* x;
+};
+
 // Where an update-row kernel that emits the list itself puts it: the
 // ascending listed columns, their coefficients and the count, on the device
 // and (optional, null when off) mirrored into mapped host memory.
@@ -475,6 +503,18 @@ hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, do
                               int64_t ld, hipStream_t s);
 // panel_count, panel_offsets and panel_write for one panel, in that order.
 hipError_t panel_sparse(int width, const milp_kernels::PanelSparseArgs& args, hipStream_t s);
+// Row sums for a panel of `width` (1, 4 or 16) points in one pass over the
+// rows of [A | I] (panel_kernels.hip row_sums_panel_kernel).
+hipError_t row_sums_panel(int width, const milp_kernels::RowPanelArgs& args, hipStream_t s);
+// out[col * width + v] = in[v * ld + col] for v < kp, 0.0 for kp <= v < width.
+hipError_t panel_interleave(int width, const double* in, int64_t ld, int ncols, int kp,
+                            double* out, hipStream_t s);
+// out[col * width + v] = base[col] for v < kp, 0.0 for kp <= v < width.
+hipError_t panel_fill(int width, const double* base, int ncols, int kp, double* out,
+                      hipStream_t s);
+// num_overrides = starts[kp] - starts[0] (known to the host).
+hipError_t panel_override(int width, const milp_kernels::RowPanelOverrideArgs& args,
+                          int64_t num_overrides, hipStream_t s);
 hipError_t dense_pack(const int64_t* starts, const double* vals, const int32_t* dense_cols,
                       int nd, int m, double* body, double* tail, hipStream_t s);
 hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hipStream_t s);

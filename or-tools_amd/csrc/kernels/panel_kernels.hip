@@ -17,6 +17,10 @@
 // filters out[col * K + v] by a column mask and a drop tolerance and packs
 // the kept (column, value) pairs per vector in increasing column order; it
 // replaces deinterleave_kernel when the caller wants sparse rows.
+//
+// The other direction, row sums [A | I] x for a panel of K points
+// (row_sums_panel_kernel and the kernels that build its interleaved points:
+// interleave, panel_fill, panel_override), follows the sparse form.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -346,6 +350,105 @@ __global__ __launch_bounds__(kPanelTileColumns) void panel_write_kernel(PanelSpa
   }
 }
 
+// ---------------------------------------------------------------------------
+// Row sums [A | I] x for a panel of K points in one pass over the rows
+// (include/mi_lp.h mi_lp_column_combinations): row_sum_kernel's sum
+// (simplex_kernels.hip; variable_values.cc:101-131, sparse.h:389-399) for K
+// points, without mask and sign. Per (row, point): from +0.0, the row's
+// entries in increasing column order, acc = acc + x[col] * a, an entry whose
+// multiplier is +-0.0 left out, every product and sum rounded separately.
+//
+// The points are column-interleaved, X[col * K + v]. Thread t owns the pair
+// (row t / K of the workgroup's 256 / K rows, point t % K) and walks the row
+// strictly in order. The K lanes of a row are adjacent: an entry's (col, val)
+// is one address for all of them and its K multipliers are one contiguous
+// read (128 B at K = 16). The entries are read directly: a row's lanes stream
+// it front to back, so each of its cache lines is fetched once. The gathers
+// of kRowPanelUnroll entries are issued before the ordered adds that consume
+// them. A skipped term is added as -0.0, which leaves every sum's bits
+// unchanged (x + -0.0 == x, also for x = +-0.0) and the lanes converged.
+template <int K>
+__global__ __launch_bounds__(kRowPanelThreads) void row_sums_panel_kernel(RowPanelArgs a) {
+  static_assert(kRowPanelThreads % K == 0, "whole rows per workgroup");
+  constexpr int kRows = kRowPanelThreads / K;
+  const int v = threadIdx.x % K;
+  const int row = blockIdx.x * kRows + threadIdx.x / K;
+  if (row >= a.num_rows) return;  // no barrier and no cross-lane step below
+  const int64_t s = a.t_starts[row];
+  const int64_t e = a.t_starts[row + 1];
+  const double* __restrict__ x = a.x + v;
+  double acc = 0.0;
+  int64_t i = s;
+  for (; i + kRowPanelUnroll <= e; i += kRowPanelUnroll) {
+    int col[kRowPanelUnroll];
+    double val[kRowPanelUnroll];
+    double mult[kRowPanelUnroll];
+#pragma unroll
+    for (int u = 0; u < kRowPanelUnroll; ++u) {
+      col[u] = a.t_cols[i + u];
+      val[u] = a.t_vals[i + u];
+    }
+#pragma unroll
+    for (int u = 0; u < kRowPanelUnroll; ++u) mult[u] = x[static_cast<int64_t>(col[u]) * K];
+#pragma unroll
+    for (int u = 0; u < kRowPanelUnroll; ++u) acc += mult[u] != 0.0 ? mult[u] * val[u] : -0.0;
+  }
+  for (; i < e; ++i) {
+    const double mult = x[static_cast<int64_t>(a.t_cols[i]) * K];
+    acc += mult != 0.0 ? mult * a.t_vals[i] : -0.0;
+  }
+  if (v < a.kp) a.out[static_cast<int64_t>(row) * K + v] = acc;
+}
+
+// out[col * K + v] = in[v * ld + col] for v < kp and 0.0 for the padding
+// points: deinterleave_kernel backwards, 64 columns through LDS so that both
+// sides are contiguous.
+template <int K>
+__global__ __launch_bounds__(256) void interleave_kernel(const double* __restrict__ in,
+                                                         int64_t ld, int ncols, int kp,
+                                                         double* __restrict__ out) {
+  __shared__ double tile[64 * (K + 1)];
+  const int c0 = blockIdx.x * 64;
+  const int cols = min(64, ncols - c0);
+  for (int i = threadIdx.x; i < 64 * kp; i += 256) {
+    const int v = i >> 6;
+    const int cl = i & 63;
+    if (cl < cols) tile[cl * (K + 1) + v] = in[v * ld + c0 + cl];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < cols * K; i += 256) {
+    const int v = i % K;
+    out[static_cast<int64_t>(c0) * K + i] = v < kp ? tile[(i / K) * (K + 1) + v] : 0.0;
+  }
+}
+
+// out[col * K + v] = base[col] for v < kp and 0.0 for the padding points.
+template <int K>
+__global__ __launch_bounds__(256) void panel_fill_kernel(const double* __restrict__ base,
+                                                         int ncols, int kp,
+                                                         double* __restrict__ out) {
+  const int64_t total = static_cast<int64_t>(ncols) * K;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < total; i += stride) {
+    out[i] = static_cast<int>(i % K) < kp ? base[i / K] : 0.0;
+  }
+}
+
+// Override i of the panel belongs to the point v with starts[v] <= i <
+// starts[v + 1] (at most 16 points: a linear search).
+template <int K>
+__global__ __launch_bounds__(256) void panel_override_kernel(RowPanelOverrideArgs a) {
+  const int64_t first = a.starts[0];
+  const int64_t last = a.starts[a.kp];
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
+  for (int64_t i = first + static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < last;
+       i += stride) {
+    int v = 0;
+    while (v + 1 < a.kp && a.starts[v + 1] <= i) ++v;
+    a.x[static_cast<int64_t>(a.cols[i]) * K + v] = a.vals[i];
+  }
+}
+
 }  // namespace milp_kernels
 
 namespace milp_launch {
@@ -414,6 +517,63 @@ hipError_t panel_sparse(int width, const PanelSparseArgs& args, hipStream_t s) {
     case 1: panel_write_kernel<1><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
     case 4: panel_write_kernel<4><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
     default: panel_write_kernel<16><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t row_sums_panel(int width, const RowPanelArgs& args, hipStream_t s) {
+  if (args.num_rows <= 0 || args.kp <= 0) return hipSuccess;
+  if (width != 1 && width != 4 && width != 16) return hipErrorInvalidValue;
+  const int blocks = panel_div_up(args.num_rows, kRowPanelThreads / width);
+  switch (width) {
+    case 1: row_sums_panel_kernel<1><<<blocks, kRowPanelThreads, 0, s>>>(args); break;
+    case 4: row_sums_panel_kernel<4><<<blocks, kRowPanelThreads, 0, s>>>(args); break;
+    default: row_sums_panel_kernel<16><<<blocks, kRowPanelThreads, 0, s>>>(args); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t panel_interleave(int width, const double* in, int64_t ld, int ncols, int kp,
+                            double* out, hipStream_t s) {
+  if (ncols <= 0) return hipSuccess;
+  const int blocks = panel_div_up(ncols, 64);
+  switch (width) {
+    case 1: interleave_kernel<1><<<blocks, 256, 0, s>>>(in, ld, ncols, kp, out); break;
+    case 4: interleave_kernel<4><<<blocks, 256, 0, s>>>(in, ld, ncols, kp, out); break;
+    case 16: interleave_kernel<16><<<blocks, 256, 0, s>>>(in, ld, ncols, kp, out); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// Grid-stride kernels: at most 2048 workgroups.
+static inline int panel_stride_blocks(int64_t elements) {
+  const int64_t blocks = (elements + 255) / 256;
+  return static_cast<int>(blocks < 2048 ? blocks : 2048);
+}
+
+hipError_t panel_fill(int width, const double* base, int ncols, int kp, double* out,
+                      hipStream_t s) {
+  if (ncols <= 0) return hipSuccess;
+  const int blocks = panel_stride_blocks(static_cast<int64_t>(ncols) * width);
+  switch (width) {
+    case 1: panel_fill_kernel<1><<<blocks, 256, 0, s>>>(base, ncols, kp, out); break;
+    case 4: panel_fill_kernel<4><<<blocks, 256, 0, s>>>(base, ncols, kp, out); break;
+    case 16: panel_fill_kernel<16><<<blocks, 256, 0, s>>>(base, ncols, kp, out); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t panel_override(int width, const RowPanelOverrideArgs& args, int64_t num_overrides,
+                          hipStream_t s) {
+  if (num_overrides <= 0 || args.kp <= 0) return hipSuccess;
+  const int blocks = panel_stride_blocks(num_overrides);
+  switch (width) {
+    case 1: panel_override_kernel<1><<<blocks, 256, 0, s>>>(args); break;
+    case 4: panel_override_kernel<4><<<blocks, 256, 0, s>>>(args); break;
+    case 16: panel_override_kernel<16><<<blocks, 256, 0, s>>>(args); break;
+    default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }

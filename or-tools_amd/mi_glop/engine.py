@@ -121,6 +121,8 @@ def lib():
     L.mi_lp_get_tableau_rows_sparse.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_double,
                                                 ctypes.c_uint32, vp, vp]
     L.mi_lp_get_sparse_rows.argtypes = [vp, vp, vp]
+    L.mi_lp_column_combinations.argtypes = [vp, vp, ctypes.c_int32, vp]
+    L.mi_lp_column_combinations_from.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp]
     L.mi_lp_solver_params_default.argtypes = [ctypes.POINTER(abi.MiLpSolverParams)]
     L.mi_lp_scale.argtypes = [ctypes.POINTER(abi.MiLpSolverParams), ctypes.c_int32,
                               ctypes.c_int32] + [vp] * 14
@@ -573,6 +575,58 @@ class LpHandle:
                    None if left is None else _p(left))
         out = self._sparse_rows(starts, k)
         return out + (left[:k],) if with_left_inverses else out
+
+    def _points(self, X, what):
+        """X as a contiguous (k, n+m) array: (k, n) gets zero slacks appended,
+        a 1-D array is one point."""
+        n, total = self.lp.n, self.lp.n + self.lp.m
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X[None, :]
+        if X.ndim != 2 or X.shape[1] not in (n, total):
+            raise ValueError(f"{what} must be (k, {total}) or (k, {n}), got {X.shape}")
+        if X.shape[1] != total:
+            X = np.concatenate([X, np.zeros((X.shape[0], total - X.shape[1]))], axis=1)
+        return X
+
+    def column_combinations(self, X):
+        """X: (k, n+m), or (k, n) (zero slacks are appended), or 1-D for k = 1.
+        Returns the (k, m) array of the row sums [A | I] X[j] (entries of a row
+        in increasing column order, zero multipliers skipped), computed on the
+        GPU with A read once per 16 points."""
+        X = self._points(X, "X")
+        k = X.shape[0]
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            X = np.zeros((1, self.lp.n + self.lp.m), np.float64)
+        out = np.zeros((max(k, 1), self.lp.m), np.float64)
+        self._call("column_combinations", _p(X), k, _p(out))
+        return out[:k]
+
+    def column_combinations_from(self, base, overrides):
+        """column_combinations of the points base with X[j][cols] = vals for
+        overrides[j] = (cols, vals), built on the GPU: only base (n or n+m
+        values) and the override lists go up. No column twice within a point.
+        Returns (k, m)."""
+        base = self._points(base, "base")
+        if base.shape[0] != 1:
+            raise ValueError("base must be one point")
+        k = len(overrides)
+        starts = np.zeros(k + 1, np.int64)
+        cols, vals = [np.zeros(0, np.int32)], [np.zeros(0, np.float64)]
+        for j, (c, v) in enumerate(overrides):
+            c = np.ascontiguousarray(c, dtype=np.int32).reshape(-1)
+            v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+            if len(c) != len(v):
+                raise ValueError(f"overrides[{j}]: {len(c)} columns, {len(v)} values")
+            cols.append(c)
+            vals.append(v)
+            starts[j + 1] = starts[j] + len(c)
+        cols = np.ascontiguousarray(np.concatenate(cols))
+        vals = np.ascontiguousarray(np.concatenate(vals))
+        out = np.zeros((max(k, 1), self.lp.m), np.float64)
+        self._call("column_combinations_from", _p(base), k, _p(starts),
+                   _p(cols) if len(cols) else None, _p(vals) if len(vals) else None, _p(out))
+        return out[:k]
 
 
 def batch_solve(handles, num_threads=4, progress=None, progress_s=15.0):
