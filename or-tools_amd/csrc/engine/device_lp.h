@@ -41,6 +41,8 @@ void SdualShutdown();
 void RegisterDeviceShutdown();
 
 class CompactSparseMatrix;
+struct PanelWorkspace;  // device_panel.h
+class PanelTimer;       // device_panel.hip
 
 // Records the device operation under way (MILP_WATCHDOG_S diagnostics).
 void DeviceOp(const char* what);
@@ -51,7 +53,7 @@ struct DeviceError : public std::runtime_error {
 
 class DeviceLp : public DeviceSolver {
  public:
-  DeviceLp() = default;
+  DeviceLp();
   ~DeviceLp() override;
   DeviceLp(const DeviceLp&) = delete;
   DeviceLp& operator=(const DeviceLp&) = delete;
@@ -136,7 +138,8 @@ class DeviceLp : public DeviceSolver {
   };
   LastColumnDots last_column_dots() const { return last_column_dots_; }
 
-  // --- column dots of k vectors in one pass (kernels/panel_kernels.hip) ----
+  // --- column dots of k vectors in one pass (device_panel.hip, kernels/
+  // panel_kernels.hip) ----
   // out[j * N + col] = a_col . y_j (ColumnScalarProduct's order, sparse.h:
   // 514-542) for j < k and every column of [A | I]: no mask, no drop
   // tolerance. y is k x m and out k x N, both vector-major on the host. The
@@ -145,11 +148,11 @@ class DeviceLp : public DeviceSolver {
   // is read once per panel. Synchronizes before it returns.
   // The panel's device buffers (interleaved vectors, interleaved and
   // vector-major results: 8 m W + 8 N W + 8 N min(k, 16) bytes at width W)
-  // are its own, allocated at first use, grown as needed and freed with the
-  // handle; at config 5's size (N = 1.1 M) one 16-vector output panel is
-  // 141 MB. Nothing a solve reads is written: not the update row, its list or
-  // flags, the masks, the dual-mode arrays or last_paths(). Not counted in
-  // mi_lp_kernel_stats (its ids are taken).
+  // are the panel workspace's (device_panel.h), allocated at first use, grown
+  // as needed and freed with the handle; at config 5's size (N = 1.1 M) one
+  // 16-vector output panel is 141 MB. Nothing a solve reads is written: not
+  // the update row, its list or flags, the masks, the dual-mode arrays or
+  // last_paths(). Not counted in mi_lp_kernel_stats (its ids are taken).
   void ColumnDotsPanel(const double* y, int k, double* out);
   // Which kernels the last ColumnDotsPanel went through (test record).
   enum PanelSparse { kPanelNone = 0, kPanelShortColumns = 1, kPanelLongColumns = 2 };
@@ -158,8 +161,16 @@ class DeviceLp : public DeviceSolver {
     bool dense = false;       // the dense-block kernel ran
     int panels = 0;
     int width = 0;            // of the last panel
+    // Joins a column shard's record: any shard's kernels, the last shard's
+    // panels and width.
+    void Merge(const LastPanel& shard) {
+      sparse = sparse > shard.sparse ? sparse : shard.sparse;
+      dense = dense || shard.dense;
+      panels = shard.panels;
+      width = shard.width;
+    }
   };
-  LastPanel last_panel() const { return last_panel_; }
+  LastPanel last_panel() const;
   // Device-event time of the panel kernels (transfers excluded) since the
   // last call, for the measurement script; events are recorded from the
   // first call on.
@@ -171,8 +182,8 @@ class DeviceLp : public DeviceSolver {
   // (strict: +-0.0 at tolerance 0 and NaN are dropped, +-inf kept). Each kept
   // value is bit for bit what ColumnDotsPanel returns. The dot launches are
   // ColumnDotsPanel's; then panel_count / panel_offsets / panel_write pack
-  // d_panel_i_ on the device, and only the per-vector counts and the kept
-  // (4-byte column, 8-byte value) entries come down: no transfer grows with
+  // the interleaved results on the device, and only the per-vector counts and
+  // the kept (4-byte column, 8-byte value) entries come down: no transfer grows with
   // N. Same buffers as ColumnDotsPanel plus the packed columns (4 N min(k,
   // 16) bytes), the mask and the per-tile counts and offsets; the same
   // solve state is left alone. Synchronizes before it returns.
@@ -190,7 +201,7 @@ class DeviceLp : public DeviceSolver {
     int64_t kept = 0;        // entries of all rows
     int64_t bytes_down = 0;  // device-to-host bytes of the call
   };
-  LastPanelSparse last_panel_sparse() const { return last_panel_sparse_; }
+  LastPanelSparse last_panel_sparse() const;
   // The sparse-row kernels' tile and the offsets kernel's scan step
   // (kernel_args.h kPanelTileColumns, kPanelOffsetsStep), for the tests.
   static int PanelTileColumns();
@@ -204,19 +215,20 @@ class DeviceLp : public DeviceSolver {
   void RowSums(const std::vector<double>& x, bool skip_basic, double sign,
                std::vector<double>* out);
 
-  // --- row sums of k points in one pass (kernels/panel_kernels.hip) -----
+  // --- row sums of k points in one pass (device_panel.hip, kernels/
+  // panel_kernels.hip) -----
   // out[j * m + r] = RowSums(x_j, false, 1.0)[r] bit for bit, for j < k: from
   // +0.0, row r's entries in increasing column order, acc = acc + x_j[col] * a,
   // entries with x_j[col] == +-0.0 left out. x is k x N and out k x m, both
   // vector-major on the host. The points go up vector-major in panels of up
   // to 16 (widths 1, 4 and 16, padded with zero points whose results are not
   // stored) and are interleaved on the device; the CSR of [A | I] is read
-  // once per panel. Uses ColumnDotsPanel's buffers with the roles swapped
-  // (d_panel_i_: the interleaved points, d_panel_y_: the interleaved
-  // results, d_panel_out_: vector-major staging of both) and, like it, writes
-  // nothing a solve reads and has no id in mi_lp_kernel_stats; its kernel
-  // time is in TakePanelKernelMs. With column shards it stays on the unsplit
-  // handle, as RowSums does. Synchronizes before it returns.
+  // once per panel. Shares the panel workspace's three shape-named buffers
+  // with ColumnDotsPanel (device_panel.h says what each direction keeps in
+  // each) and, like it, writes nothing a solve reads and has no id in
+  // mi_lp_kernel_stats; its kernel time is in TakePanelKernelMs. With column
+  // shards it stays on the unsplit handle, as RowSums does. Synchronizes
+  // before it returns.
   void RowSumsPanel(const double* x, int k, double* out);
   // The same for the points x_j = base (N values) with x_j[cols[i]] = vals[i]
   // for i in [starts[j], starts[j + 1]), built on the device: base, starts,
@@ -236,7 +248,7 @@ class DeviceLp : public DeviceSolver {
     int kernel = kRowPanelNone;      // path of the last panel
     int64_t overrides_up_bytes = 0;  // host-to-device bytes of a RowSumsPanelFrom call
   };
-  LastRowPanel last_row_panel() const { return last_row_panel_; }
+  LastRowPanel last_row_panel() const;
   // Rows per workgroup of row_sums_panel_kernel at widths 1, 4 and 16, and
   // its staging chunk length (0: it reads the rows directly), for the tests.
   static void RowPanelGeometry(int rows_per_workgroup[3], int* chunk);
@@ -478,49 +490,19 @@ class DeviceLp : public DeviceSolver {
                                     const uint64_t* keep_words, SparseRows* out);
   void ShardedStats();
   void FlushOwnMasks();
-  // ColumnDotsPanel's own buffers (not in allocations_: they outlive a
-  // matrix upload and are sized by capacity).
-  void PanelReserve(int width, int kp);
-  void FreePanelBuffers();
-  double* d_panel_y_ = nullptr;    // interleaved vectors, m x width
-  double* h_panel_y_ = nullptr;    // pinned staging of it
-  double* d_panel_i_ = nullptr;    // interleaved results, N x width
-  double* d_panel_out_ = nullptr;  // vector-major results, kp x N; or the packed kept values
-  size_t panel_y_cap_ = 0, panel_i_cap_ = 0, panel_out_cap_ = 0;  // doubles
-  LastPanel last_panel_;
-  // The launch sequence both panel calls share (device_lp.hip).
-  struct PanelPlan {
+  // The panel calls (device_panel.hip): their buffers, timing events and
+  // test records are the workspace's, one per handle (each shard has its own).
+  std::unique_ptr<PanelWorkspace> panel_;
+  struct PanelPlan {  // the kernel choice, LaunchColumnDots' rule
     bool long_columns = false;
     int sparse_cols = 0;
   };
-  PanelPlan PanelBegin();
-  void PanelDots(const PanelPlan& plan, const double* y, int first, int kp, int width);
-  void PanelKernelsLaunched();
-  void PanelDone(const PanelPlan& plan, int width, LastPanel* record);
-  // ColumnDotsPanelSparse's additions, kept like the buffers above.
-  void PanelSparseReserve(int kp, int tiles);
-  int32_t* d_panel_cols_ = nullptr;     // packed kept columns, <= N x kp
-  uint64_t* d_panel_mask_ = nullptr;    // keep mask, ceil(N / 64) words
-  int* d_panel_counts_ = nullptr;       // kp x tiles
-  int64_t* d_panel_offsets_ = nullptr;  // kp x tiles, then the kp totals
-  int64_t* h_panel_totals_ = nullptr;   // pinned, kPanelMaxWidth
-  size_t panel_cols_cap_ = 0, panel_mask_cap_ = 0, panel_counts_cap_ = 0,
-         panel_offsets_cap_ = 0;  // bytes
-  LastPanelSparse last_panel_sparse_;
-  // RowSumsPanel's additions, kept like the buffers above.
-  void RowPanelReserveOverrides(int k, int64_t overrides);
-  void RowPanelSums(int first, int kp, int width, double* out);
-  void PanelAddKernelMs();
-  double* d_panel_base_ = nullptr;          // the base point, N
-  int64_t* d_panel_ov_starts_ = nullptr;    // k + 1
-  int32_t* d_panel_ov_cols_ = nullptr;      // overrides of the whole call
-  double* d_panel_ov_vals_ = nullptr;
-  size_t panel_base_cap_ = 0, panel_ov_starts_cap_ = 0, panel_ov_cols_cap_ = 0,
-         panel_ov_vals_cap_ = 0;  // bytes
-  LastRowPanel last_row_panel_;
-  bool panel_timing_ = false;
-  double panel_kernel_ms_ = 0.0;
-  void* ev_panel_[2] = {nullptr, nullptr};
+  PanelPlan PanelKernelChoice() const;
+  void PanelReserve(int width, int kp);
+  void PanelUploadVectors(const double* y, int first, int kp, int width);
+  void PanelLaunchDots(const PanelPlan& plan, int kp, int width);
+  void PanelRecord(const PanelPlan& plan, int width, LastPanel* record) const;
+  void RowPanelSums(int first, int kp, int width, PanelTimer* timer, double* out);
   bool is_shard_ = false;
   std::vector<std::unique_ptr<DeviceLp>> shards_;  // null: a block owned by another process
   ExchangeFn exchange_fn_ = nullptr;

@@ -1,5 +1,6 @@
 // DeviceLp: device buffers + kernel launch plumbing (see device_lp.h).
 #include "device_lp.h"
+#include "device_panel.h"  // ~DeviceLp frees the panel workspace
 #include "fibers.h"
 #include "host_pool.h"
 
@@ -68,7 +69,7 @@ DeviceLp::~DeviceLp() {
   if (stream_ != nullptr) (void)hipStreamSynchronize(S(stream_));
   SdualFree();
   FreeTriBuffers();
-  FreePanelBuffers();
+  panel_.reset();
   for (void* p : allocations_) (void)hipFree(p);
   if (h_pin_i_) (void)hipHostFree(h_pin_i_);
   if (h_pin_d_) (void)hipHostFree(h_pin_d_);
@@ -1644,394 +1645,6 @@ void DeviceLp::Pricing(const std::vector<double>& c, const std::vector<double>& 
   Download(h_pin_d_, d_out_n_, n_total_ * sizeof(double));
   CopyHost(rc->data(), h_pin_d_, n_total_ * sizeof(double));
   if (fused && n_list > 0) CopyHost(list_dots->data(), h_pin_d2_, n_list * sizeof(double));
-}
-
-void DeviceLp::FreePanelBuffers() {
-  if (d_panel_y_) (void)hipFree(d_panel_y_);
-  if (d_panel_i_) (void)hipFree(d_panel_i_);
-  if (d_panel_out_) (void)hipFree(d_panel_out_);
-  if (h_panel_y_) (void)hipHostFree(h_panel_y_);
-  d_panel_y_ = d_panel_i_ = d_panel_out_ = h_panel_y_ = nullptr;
-  panel_y_cap_ = panel_i_cap_ = panel_out_cap_ = 0;
-  if (d_panel_cols_) (void)hipFree(d_panel_cols_);
-  if (d_panel_mask_) (void)hipFree(d_panel_mask_);
-  if (d_panel_counts_) (void)hipFree(d_panel_counts_);
-  if (d_panel_offsets_) (void)hipFree(d_panel_offsets_);
-  if (h_panel_totals_) (void)hipHostFree(h_panel_totals_);
-  d_panel_cols_ = nullptr;
-  d_panel_mask_ = nullptr;
-  d_panel_counts_ = nullptr;
-  d_panel_offsets_ = h_panel_totals_ = nullptr;
-  panel_cols_cap_ = panel_mask_cap_ = panel_counts_cap_ = panel_offsets_cap_ = 0;
-  if (d_panel_base_) (void)hipFree(d_panel_base_);
-  if (d_panel_ov_starts_) (void)hipFree(d_panel_ov_starts_);
-  if (d_panel_ov_cols_) (void)hipFree(d_panel_ov_cols_);
-  if (d_panel_ov_vals_) (void)hipFree(d_panel_ov_vals_);
-  d_panel_base_ = d_panel_ov_vals_ = nullptr;
-  d_panel_ov_starts_ = nullptr;
-  d_panel_ov_cols_ = nullptr;
-  panel_base_cap_ = panel_ov_starts_cap_ = panel_ov_cols_cap_ = panel_ov_vals_cap_ = 0;
-  for (void*& e : ev_panel_) {
-    if (e) (void)hipEventDestroy(reinterpret_cast<hipEvent_t>(e));
-    e = nullptr;
-  }
-}
-
-// Grows the panel buffers to one panel of `width` holding `kp` vectors. The
-// stream is idle between panels (each ends with a synchronizing download).
-void DeviceLp::PanelReserve(int width, int kp) {
-  const auto grow = [this](double** p, size_t* cap, size_t n, const char* what) {
-    if (n <= *cap) return;
-    if (*p) Check(hipFree(*p), what);
-    *p = nullptr;
-    *cap = 0;
-    Check(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(double)), what);
-    *cap = n;
-  };
-  const size_t ym = std::max<size_t>(1, size_t(m_) * width);
-  if (ym > panel_y_cap_) {
-    if (h_panel_y_) Check(hipHostFree(h_panel_y_), "panel staging");
-    h_panel_y_ = nullptr;
-    Check(hipHostMalloc(reinterpret_cast<void**>(&h_panel_y_), ym * sizeof(double)),
-          "panel staging");
-  }
-  grow(&d_panel_y_, &panel_y_cap_, ym, "panel vectors");
-  grow(&d_panel_i_, &panel_i_cap_, size_t(n_total_) * width, "panel results");
-  grow(&d_panel_out_, &panel_out_cap_, size_t(n_total_) * kp, "panel output");
-}
-
-double DeviceLp::TakePanelKernelMs() {
-  double ms = panel_kernel_ms_;
-  panel_kernel_ms_ = 0.0;
-  panel_timing_ = true;
-  for (auto& d : shards_) {
-    if (d) ms += d->TakePanelKernelMs();
-  }
-  return ms;
-}
-
-// What the dense and the sparse panel call share: the kernel choice
-// (LaunchColumnDots' rule) and the timing events, then per panel the y
-// interleave, its upload and the dot launches into d_panel_i_.
-DeviceLp::PanelPlan DeviceLp::PanelBegin() {
-  PanelPlan plan;
-  const double sparse_avg =
-      (nd_ > 0 ? (ns_ > 0 ? double(sparse_entries_) / ns_ : 0.0) : avg_col_len_);
-  plan.long_columns = sparse_avg >= 32.0;  // LaunchColumnDots' rule
-  plan.sparse_cols = nd_ > 0 ? ns_ : n_total_;
-  if (panel_timing_ && ev_panel_[0] == nullptr) {
-    for (void*& e : ev_panel_) {
-      hipEvent_t ev;
-      Check(hipEventCreate(&ev), "hipEventCreate");
-      e = ev;
-    }
-  }
-  return plan;
-}
-
-void DeviceLp::PanelDots(const PanelPlan& plan, const double* y, int first, int kp, int width) {
-  PanelReserve(width, kp);
-  for (int r = 0; r < m_; ++r) {
-    double* dst = h_panel_y_ + size_t(r) * width;
-    for (int v = 0; v < kp; ++v) dst[v] = y[size_t(first + v) * m_ + r];
-    for (int v = kp; v < width; ++v) dst[v] = 0.0;
-  }
-  Upload(d_panel_y_, h_panel_y_, size_t(m_) * width * sizeof(double));
-  if (panel_timing_) {
-    Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
-  }
-  milp_kernels::PanelDotArgs a{};
-  a.starts = d_starts_;
-  a.rows = d_rows_;
-  a.vals = d_vals_;
-  a.y = d_panel_y_;
-  a.ncols = plan.sparse_cols;
-  a.col_list = nd_ > 0 ? d_sparse_cols_ : nullptr;
-  a.kp = kp;
-  a.out = d_panel_i_;
-  Check(milp_launch::column_dot_panel(width, plan.long_columns, a, S(stream_)),
-        "column dots panel");
-  if (nd_ > 0) {
-    milp_kernels::PanelDenseArgs d{};
-    d.body = d_dense_body_;
-    d.tail = d_dense_tail_;
-    d.dense_cols = d_dense_cols_;
-    d.nd = nd_;
-    d.m = m_;
-    d.y = d_panel_y_;
-    d.kp = kp;
-    d.out = d_panel_i_;
-    Check(milp_launch::dense_dot_panel(width, d, S(stream_)), "dense dots panel");
-  }
-}
-
-// After the panel's last kernel launch, before its synchronizing download.
-void DeviceLp::PanelKernelsLaunched() {
-  if (panel_timing_) {
-    Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[1]), S(stream_)), "ev");
-  }
-}
-
-// After that download: the kernel time and the record of the panel.
-void DeviceLp::PanelAddKernelMs() {
-  if (panel_timing_) {
-    float ms = 0.0f;
-    Check(hipEventElapsedTime(&ms, reinterpret_cast<hipEvent_t>(ev_panel_[0]),
-                              reinterpret_cast<hipEvent_t>(ev_panel_[1])),
-          "ev time");
-    panel_kernel_ms_ += ms;
-  }
-}
-
-void DeviceLp::PanelDone(const PanelPlan& plan, int width, LastPanel* record) {
-  PanelAddKernelMs();
-  record->sparse = plan.sparse_cols > 0
-                       ? (plan.long_columns ? kPanelLongColumns : kPanelShortColumns)
-                       : kPanelNone;
-  record->dense = nd_ > 0;
-  record->panels += 1;
-  record->width = width;
-}
-
-static int PanelWidth(int kp) { return kp == 1 ? 1 : (kp <= 4 ? 4 : 16); }
-
-void DeviceLp::ColumnDotsPanel(const double* y, int k, double* out) {
-  if (!shards_.empty()) return ShardedColumnDotsPanel(y, k, out);
-  last_panel_ = LastPanel();
-  if (k <= 0 || n_total_ <= 0) return;
-  DeviceOp("column dots panel");
-  const PanelPlan plan = PanelBegin();
-  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
-    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
-    const int width = PanelWidth(kp);
-    PanelDots(plan, y, first, kp, width);
-    Check(milp_launch::panel_deinterleave(width, d_panel_i_, n_total_, kp, d_panel_out_,
-                                          n_total_, S(stream_)),
-          "panel de-interleave");
-    PanelKernelsLaunched();
-    Download(out + size_t(first) * n_total_, d_panel_out_,
-             size_t(kp) * n_total_ * sizeof(double));
-    PanelDone(plan, width, &last_panel_);
-  }
-  DeviceOp("column dots panel done");
-}
-
-int DeviceLp::PanelTileColumns() { return milp_kernels::kPanelTileColumns; }
-int DeviceLp::PanelOffsetsStepTiles() { return milp_kernels::kPanelOffsetsStep; }
-
-// Grows the sparse form's own buffers to one panel of kp vectors: the packed
-// columns (d_panel_out_ holds the packed values), the keep mask, the per
-// (vector, tile) counts and offsets with the kp totals behind the offsets, and
-// the pinned landing place of the totals.
-void DeviceLp::PanelSparseReserve(int kp, int tiles) {
-  const auto grow = [this](void** p, size_t* cap, size_t bytes, const char* what) {
-    if (bytes <= *cap) return;
-    if (*p) Check(hipFree(*p), what);
-    *p = nullptr;
-    *cap = 0;
-    Check(hipMalloc(p, bytes), what);
-    *cap = bytes;
-  };
-  grow(reinterpret_cast<void**>(&d_panel_cols_), &panel_cols_cap_,
-       size_t(n_total_) * kp * sizeof(int32_t), "panel columns");
-  grow(reinterpret_cast<void**>(&d_panel_mask_), &panel_mask_cap_,
-       size_t((n_total_ + 63) / 64) * sizeof(uint64_t), "panel mask");
-  grow(reinterpret_cast<void**>(&d_panel_counts_), &panel_counts_cap_,
-       size_t(kp) * tiles * sizeof(int), "panel counts");
-  grow(reinterpret_cast<void**>(&d_panel_offsets_), &panel_offsets_cap_,
-       (size_t(kp) * tiles + milp_kernels::kPanelMaxWidth) * sizeof(int64_t), "panel offsets");
-  if (h_panel_totals_ == nullptr) {
-    Check(hipHostMalloc(reinterpret_cast<void**>(&h_panel_totals_),
-                        milp_kernels::kPanelMaxWidth * sizeof(int64_t)),
-          "panel totals");
-  }
-}
-
-void DeviceLp::ColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
-                                     const uint64_t* keep_words, SparseRows* out) {
-  if (!shards_.empty()) {
-    return ShardedColumnDotsPanelSparse(y, k, drop_tolerance, keep_words, out);
-  }
-  last_panel_sparse_ = LastPanelSparse();
-  out->row_starts.assign(size_t(std::max(k, 0)) + 1, 0);
-  out->cols.clear();
-  out->vals.clear();
-  if (k <= 0 || n_total_ <= 0) return;
-  DeviceOp("column dots panel sparse");
-  const PanelPlan plan = PanelBegin();
-  const int tiles = (n_total_ + milp_kernels::kPanelTileColumns - 1) /
-                    milp_kernels::kPanelTileColumns;
-  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
-    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
-    const int width = PanelWidth(kp);
-    PanelDots(plan, y, first, kp, width);
-    PanelSparseReserve(kp, tiles);
-    if (first == 0 && keep_words != nullptr) {
-      Upload(d_panel_mask_, keep_words, size_t((n_total_ + 63) / 64) * sizeof(uint64_t));
-    }
-    milp_kernels::PanelSparseArgs a{};
-    a.in = d_panel_i_;
-    a.ncols = n_total_;
-    a.kp = kp;
-    a.tiles = tiles;
-    a.mask = keep_words != nullptr ? d_panel_mask_ : nullptr;
-    a.drop_tolerance = drop_tolerance;
-    a.counts = d_panel_counts_;
-    a.offsets = d_panel_offsets_;
-    a.totals = d_panel_offsets_ + size_t(kp) * tiles;
-    a.cols = d_panel_cols_;
-    a.vals = d_panel_out_;
-    Check(milp_launch::panel_sparse(width, a, S(stream_)), "panel sparse rows");
-    PanelKernelsLaunched();
-    // Down: the kp totals, then exactly the kept entries.
-    Download(h_panel_totals_, a.totals, size_t(kp) * sizeof(int64_t));
-    int64_t kept = 0;
-    for (int v = 0; v < kp; ++v) {
-      if (h_panel_totals_[v] < 0 || h_panel_totals_[v] > n_total_) {
-        throw DeviceError("panel sparse rows: bad count");
-      }
-      kept += h_panel_totals_[v];
-      out->row_starts[first + v + 1] = out->row_starts[first + v] + h_panel_totals_[v];
-    }
-    const size_t old = out->cols.size();
-    out->cols.resize(old + size_t(kept));
-    out->vals.resize(old + size_t(kept));
-    if (kept > 0) {
-      Check(hipMemcpyAsync(out->cols.data() + old, d_panel_cols_, size_t(kept) * sizeof(int32_t),
-                           hipMemcpyDeviceToHost, S(stream_)),
-            "D2H");
-      Download(out->vals.data() + old, d_panel_out_, size_t(kept) * sizeof(double));
-    }
-    PanelDone(plan, width, &last_panel_sparse_.panel);
-    last_panel_sparse_.kept += kept;
-    last_panel_sparse_.bytes_down += int64_t(kp) * 8 + kept * 12;
-  }
-  DeviceOp("column dots panel sparse done");
-}
-
-void DeviceLp::RowPanelGeometry(int rows_per_workgroup[3], int* chunk) {
-  rows_per_workgroup[0] = milp_kernels::kRowPanelThreads;
-  rows_per_workgroup[1] = milp_kernels::kRowPanelThreads / 4;
-  rows_per_workgroup[2] = milp_kernels::kRowPanelThreads / 16;
-  *chunk = milp_kernels::kRowPanelChunk;
-}
-
-bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const int32_t* cols) {
-  if (k < 0 || starts[0] != 0) return false;
-  for (int j = 0; j < k; ++j) {
-    if (starts[j + 1] < starts[j]) return false;
-  }
-  if (starts[k] == 0) return true;
-  if (cols == nullptr) return false;
-  std::vector<int32_t> stamp(size_t(std::max(num_cols, 0)), 0);  // point + 1 that last set it
-  for (int j = 0; j < k; ++j) {
-    for (int64_t i = starts[j]; i < starts[j + 1]; ++i) {
-      const int32_t c = cols[i];
-      if (c < 0 || c >= num_cols || stamp[c] == j + 1) return false;
-      stamp[c] = j + 1;
-    }
-  }
-  return true;
-}
-
-// The interleaved points of one panel are in d_panel_i_: the sums into
-// d_panel_y_, vector-major into d_panel_out_, down to out, and the record.
-void DeviceLp::RowPanelSums(int first, int kp, int width, double* out) {
-  milp_kernels::RowPanelArgs a{};
-  a.t_starts = d_t_starts_;
-  a.t_cols = d_t_cols_;
-  a.t_vals = d_t_vals_;
-  a.x = d_panel_i_;
-  a.num_rows = m_;
-  a.kp = kp;
-  a.out = d_panel_y_;
-  Check(milp_launch::row_sums_panel(width, a, S(stream_)), "row sums panel");
-  Check(milp_launch::panel_deinterleave(width, d_panel_y_, m_, kp, d_panel_out_, m_, S(stream_)),
-        "row panel de-interleave");
-  PanelKernelsLaunched();
-  Download(out + size_t(first) * m_, d_panel_out_, size_t(kp) * m_ * sizeof(double));
-  PanelAddKernelMs();
-  last_row_panel_.panels += 1;
-  last_row_panel_.width = width;
-  last_row_panel_.kernel = kRowPanelDirect;
-}
-
-void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
-  last_row_panel_ = LastRowPanel();
-  if (k <= 0 || m_ <= 0) return;
-  DeviceOp("row sums panel");
-  (void)PanelBegin();  // the timing events
-  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
-    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
-    const int width = PanelWidth(kp);
-    PanelReserve(width, kp);
-    Upload(d_panel_out_, x + size_t(first) * n_total_, size_t(kp) * n_total_ * sizeof(double));
-    if (panel_timing_) {
-      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
-    }
-    Check(milp_launch::panel_interleave(width, d_panel_out_, n_total_, n_total_, kp, d_panel_i_,
-                                        S(stream_)),
-          "row panel interleave");
-    RowPanelSums(first, kp, width, out);
-  }
-  DeviceOp("row sums panel done");
-}
-
-// Grows the override call's own buffers: the base point and the call's
-// starts, columns and values.
-void DeviceLp::RowPanelReserveOverrides(int k, int64_t overrides) {
-  const auto grow = [this](void** p, size_t* cap, size_t bytes, const char* what) {
-    if (bytes <= *cap) return;
-    if (*p) Check(hipFree(*p), what);
-    *p = nullptr;
-    *cap = 0;
-    Check(hipMalloc(p, bytes), what);
-    *cap = bytes;
-  };
-  grow(reinterpret_cast<void**>(&d_panel_base_), &panel_base_cap_,
-       size_t(n_total_) * sizeof(double), "panel base point");
-  grow(reinterpret_cast<void**>(&d_panel_ov_starts_), &panel_ov_starts_cap_,
-       (size_t(k) + 1) * sizeof(int64_t), "panel override starts");
-  grow(reinterpret_cast<void**>(&d_panel_ov_cols_), &panel_ov_cols_cap_,
-       size_t(overrides) * sizeof(int32_t), "panel override columns");
-  grow(reinterpret_cast<void**>(&d_panel_ov_vals_), &panel_ov_vals_cap_,
-       size_t(overrides) * sizeof(double), "panel override values");
-}
-
-void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts,
-                                const int32_t* cols, const double* vals, double* out) {
-  last_row_panel_ = LastRowPanel();
-  if (k <= 0 || m_ <= 0) return;
-  DeviceOp("row sums panel from");
-  (void)PanelBegin();  // the timing events
-  const int64_t overrides = starts[k];
-  RowPanelReserveOverrides(k, overrides);
-  Upload(d_panel_base_, base, size_t(n_total_) * sizeof(double));
-  Upload(d_panel_ov_starts_, starts, (size_t(k) + 1) * sizeof(int64_t));
-  Upload(d_panel_ov_cols_, cols, size_t(overrides) * sizeof(int32_t));
-  Upload(d_panel_ov_vals_, vals, size_t(overrides) * sizeof(double));
-  last_row_panel_.overrides_up_bytes =
-      8 * int64_t(n_total_) + 12 * overrides + 8 * (int64_t(k) + 1);
-  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
-    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
-    const int width = PanelWidth(kp);
-    PanelReserve(width, kp);
-    if (panel_timing_) {
-      Check(hipEventRecord(reinterpret_cast<hipEvent_t>(ev_panel_[0]), S(stream_)), "ev");
-    }
-    Check(milp_launch::panel_fill(width, d_panel_base_, n_total_, kp, d_panel_i_, S(stream_)),
-          "row panel fill");
-    milp_kernels::RowPanelOverrideArgs o{};
-    o.starts = d_panel_ov_starts_ + first;
-    o.cols = d_panel_ov_cols_;
-    o.vals = d_panel_ov_vals_;
-    o.kp = kp;
-    o.x = d_panel_i_;
-    Check(milp_launch::panel_override(width, o, starts[first + kp] - starts[first], S(stream_)),
-          "row panel overrides");
-    RowPanelSums(first, kp, width, out);
-  }
-  DeviceOp("row sums panel from done");
 }
 
 void DeviceLp::ColumnSquaredNorms(std::vector<double>* out) {

@@ -1,0 +1,110 @@
+// The workspace of DeviceLp's panel calls (device_panel.hip): the buffers of
+// ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel and RowSumsPanelFrom,
+// their timing events and their test records. Included by the HIP translation
+// units only; device_lp.h holds the workspace behind a pointer.
+#ifndef MILP_DEVICE_PANEL_H_
+#define MILP_DEVICE_PANEL_H_
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+
+#include "device_lp.h"
+
+namespace milp {
+
+inline void PanelCheck(hipError_t err, const char* what) {
+  if (err != hipSuccess) throw DeviceError(std::string(what) + ": " + hipGetErrorString(err));
+}
+
+// A buffer that owns its memory, device or pinned host. Capacity counts
+// elements of T and grows to exactly what is asked for; the contents are not
+// kept across a growth. Freed with the buffer: the owner sees to it that the
+// allocating device is current and no launch still uses the memory.
+template <typename T, bool kPinned>
+class PanelBuffer {
+ public:
+  PanelBuffer() = default;
+  PanelBuffer(const PanelBuffer&) = delete;
+  PanelBuffer& operator=(const PanelBuffer&) = delete;
+  ~PanelBuffer() { (void)Free(); }
+
+  T* Reserve(size_t count, const char* what) {
+    if (count > capacity_) {
+      PanelCheck(Free(), what);
+      void* p = nullptr;
+      PanelCheck(kPinned ? hipHostMalloc(&p, count * sizeof(T)) : hipMalloc(&p, count * sizeof(T)),
+                 what);
+      ptr_ = static_cast<T*>(p);
+      capacity_ = count;
+    }
+    return ptr_;
+  }
+  T* get() const { return ptr_; }
+
+ private:
+  hipError_t Free() {
+    T* p = ptr_;
+    ptr_ = nullptr;
+    capacity_ = 0;
+    if (p == nullptr) return hipSuccess;
+    return kPinned ? hipHostFree(p) : hipFree(p);
+  }
+  T* ptr_ = nullptr;
+  size_t capacity_ = 0;
+};
+template <typename T>
+using DeviceBuffer = PanelBuffer<T, false>;
+template <typename T>
+using PinnedBuffer = PanelBuffer<T, true>;
+
+// Not in DeviceLp's allocations_: the workspace outlives a matrix upload,
+// grows at first use and is freed with the handle. A panel has `width` (1, 4
+// or 16) interleaved slots of which kp are in use; m rows, N columns.
+struct PanelWorkspace {
+  PanelWorkspace() = default;
+  PanelWorkspace(const PanelWorkspace&) = delete;
+  PanelWorkspace& operator=(const PanelWorkspace&) = delete;
+  ~PanelWorkspace();
+
+  // The three buffers both directions share (PanelReserve sizes them), and
+  // what each direction keeps in them:
+  //                                   column dots (y -> a_col . y)  row sums (x -> A x)
+  //   rows: row-interleaved,          the vectors y                 the results
+  //         max(1, m width)
+  //   cols: column-interleaved,       the results                   the points x
+  //         N width
+  //   flat: vector-major, kp N        the results on their way      the points on their way
+  //                                   down (sparse form: the        up, then the results
+  //                                   packed kept values)           (kp m) on their way down
+  DeviceBuffer<double> rows, cols, flat;
+  PinnedBuffer<double> y_staging;  // column dots: the host interleave of y, max(1, m width)
+
+  // ColumnDotsPanelSparse.
+  DeviceBuffer<int32_t> kept_cols;   // packed kept columns, N kp
+  DeviceBuffer<uint64_t> keep_mask;  // ceil(N / 64) words
+  DeviceBuffer<int> counts;          // kp x tiles
+  DeviceBuffer<int64_t> offsets;     // kp x tiles, then kPanelMaxWidth totals
+  PinnedBuffer<int64_t> totals;      // kPanelMaxWidth
+
+  // RowSumsPanelFrom, uploaded once per call.
+  DeviceBuffer<double> base;        // the base point, N
+  DeviceBuffer<int64_t> ov_starts;  // k + 1
+  DeviceBuffer<int32_t> ov_cols;    // overrides of the whole call
+  DeviceBuffer<double> ov_vals;
+
+  // Kernel time (TakePanelKernelMs): off until the first take.
+  bool timing = false;
+  double kernel_ms = 0.0;
+  hipEvent_t ev[2] = {nullptr, nullptr};  // created by the first timed panel
+
+  DeviceLp::LastPanel last_panel;
+  DeviceLp::LastPanelSparse last_panel_sparse;
+  DeviceLp::LastRowPanel last_row_panel;
+};
+
+}  // namespace milp
+
+#endif  // MILP_DEVICE_PANEL_H_

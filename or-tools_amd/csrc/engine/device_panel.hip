@@ -1,0 +1,343 @@
+// DeviceLp's panel calls: k vectors per pass over [A | I] (see device_lp.h).
+// Column dots (ColumnDotsPanel, ColumnDotsPanelSparse) and row sums
+// (RowSumsPanel, RowSumsPanelFrom) share one workspace (device_panel.h), one
+// panel loop and one timing scope. No solve calls them and nothing a solve
+// reads is written.
+#include "device_panel.h"
+
+#include <algorithm>
+#include <vector>
+
+#include "../kernels/kernel_args.h"
+
+namespace milp {
+
+namespace {
+inline hipStream_t S(void* p) { return reinterpret_cast<hipStream_t>(p); }
+
+int PanelWidth(int kp) { return kp == 1 ? 1 : (kp <= 4 ? 4 : 16); }
+
+// body(first, kp, width) for the k vectors in panels of up to kPanelMaxWidth.
+template <typename Body>
+void ForEachPanel(int k, Body body) {
+  for (int first = 0; first < k; first += milp_kernels::kPanelMaxWidth) {
+    const int kp = std::min(milp_kernels::kPanelMaxWidth, k - first);
+    body(first, kp, PanelWidth(kp));
+  }
+}
+}  // namespace
+
+// The kernel time of one panel, when the workspace's timing is on: starts
+// where it is constructed, Launched() after the panel's last launch,
+// Downloaded() after the synchronizing download that follows.
+class PanelTimer {
+ public:
+  PanelTimer(PanelWorkspace* w, hipStream_t stream) : w_(w), stream_(stream) {
+    if (!w_->timing) return;
+    for (hipEvent_t& e : w_->ev) {
+      if (e == nullptr) PanelCheck(hipEventCreate(&e), "hipEventCreate");
+    }
+    PanelCheck(hipEventRecord(w_->ev[0], stream_), "ev");
+  }
+  void Launched() {
+    if (w_->timing) PanelCheck(hipEventRecord(w_->ev[1], stream_), "ev");
+  }
+  void Downloaded() {
+    if (!w_->timing) return;
+    float ms = 0.0f;
+    PanelCheck(hipEventElapsedTime(&ms, w_->ev[0], w_->ev[1]), "ev time");
+    w_->kernel_ms += ms;
+  }
+
+ private:
+  PanelWorkspace* w_;
+  hipStream_t stream_;
+};
+
+PanelWorkspace::~PanelWorkspace() {
+  for (hipEvent_t e : ev) {
+    if (e != nullptr) (void)hipEventDestroy(e);
+  }
+}
+
+DeviceLp::DeviceLp() : panel_(new PanelWorkspace) {}
+
+DeviceLp::LastPanel DeviceLp::last_panel() const { return panel_->last_panel; }
+DeviceLp::LastPanelSparse DeviceLp::last_panel_sparse() const { return panel_->last_panel_sparse; }
+DeviceLp::LastRowPanel DeviceLp::last_row_panel() const { return panel_->last_row_panel; }
+
+double DeviceLp::TakePanelKernelMs() {
+  double ms = panel_->kernel_ms;
+  panel_->kernel_ms = 0.0;
+  panel_->timing = true;
+  for (auto& d : shards_) {
+    if (d) ms += d->TakePanelKernelMs();
+  }
+  return ms;
+}
+
+int DeviceLp::PanelTileColumns() { return milp_kernels::kPanelTileColumns; }
+int DeviceLp::PanelOffsetsStepTiles() { return milp_kernels::kPanelOffsetsStep; }
+
+void DeviceLp::RowPanelGeometry(int rows_per_workgroup[3], int* chunk) {
+  rows_per_workgroup[0] = milp_kernels::kRowPanelThreads;
+  rows_per_workgroup[1] = milp_kernels::kRowPanelThreads / 4;
+  rows_per_workgroup[2] = milp_kernels::kRowPanelThreads / 16;
+  *chunk = milp_kernels::kRowPanelChunk;
+}
+
+// Grows the three shared buffers to one panel of `width` holding `kp`
+// vectors. The stream is idle between panels (each ends with a synchronizing
+// download).
+void DeviceLp::PanelReserve(int width, int kp) {
+  panel_->rows.Reserve(std::max<size_t>(1, size_t(m_) * width), "panel rows");
+  panel_->cols.Reserve(size_t(n_total_) * width, "panel columns");
+  panel_->flat.Reserve(size_t(n_total_) * kp, "panel vector-major");
+}
+
+DeviceLp::PanelPlan DeviceLp::PanelKernelChoice() const {
+  PanelPlan plan;
+  const double sparse_avg =
+      (nd_ > 0 ? (ns_ > 0 ? double(sparse_entries_) / ns_ : 0.0) : avg_col_len_);
+  plan.long_columns = sparse_avg >= 32.0;  // LaunchColumnDots' rule
+  plan.sparse_cols = nd_ > 0 ? ns_ : n_total_;
+  return plan;
+}
+
+// Vectors [first, first + kp) of y, interleaved on the host, into `rows`.
+void DeviceLp::PanelUploadVectors(const double* y, int first, int kp, int width) {
+  PanelReserve(width, kp);
+  double* staging =
+      panel_->y_staging.Reserve(std::max<size_t>(1, size_t(m_) * width), "panel staging");
+  for (int r = 0; r < m_; ++r) {
+    double* dst = staging + size_t(r) * width;
+    for (int v = 0; v < kp; ++v) dst[v] = y[size_t(first + v) * m_ + r];
+    for (int v = kp; v < width; ++v) dst[v] = 0.0;
+  }
+  Upload(panel_->rows.get(), staging, size_t(m_) * width * sizeof(double));
+}
+
+// The dots of every column with the vectors in `rows`, into `cols`.
+void DeviceLp::PanelLaunchDots(const PanelPlan& plan, int kp, int width) {
+  milp_kernels::PanelDotArgs a{};
+  a.starts = d_starts_;
+  a.rows = d_rows_;
+  a.vals = d_vals_;
+  a.y = panel_->rows.get();
+  a.ncols = plan.sparse_cols;
+  a.col_list = nd_ > 0 ? d_sparse_cols_ : nullptr;
+  a.kp = kp;
+  a.out = panel_->cols.get();
+  Check(milp_launch::column_dot_panel(width, plan.long_columns, a, S(stream_)),
+        "column dots panel");
+  if (nd_ > 0) {
+    milp_kernels::PanelDenseArgs d{};
+    d.body = d_dense_body_;
+    d.tail = d_dense_tail_;
+    d.dense_cols = d_dense_cols_;
+    d.nd = nd_;
+    d.m = m_;
+    d.y = panel_->rows.get();
+    d.kp = kp;
+    d.out = panel_->cols.get();
+    Check(milp_launch::dense_dot_panel(width, d, S(stream_)), "dense dots panel");
+  }
+}
+
+void DeviceLp::PanelRecord(const PanelPlan& plan, int width, LastPanel* record) const {
+  record->sparse = plan.sparse_cols > 0
+                       ? (plan.long_columns ? kPanelLongColumns : kPanelShortColumns)
+                       : kPanelNone;
+  record->dense = nd_ > 0;
+  record->panels += 1;
+  record->width = width;
+}
+
+void DeviceLp::ColumnDotsPanel(const double* y, int k, double* out) {
+  if (!shards_.empty()) return ShardedColumnDotsPanel(y, k, out);
+  PanelWorkspace& w = *panel_;
+  w.last_panel = LastPanel();
+  if (k <= 0 || n_total_ <= 0) return;
+  DeviceOp("column dots panel");
+  const PanelPlan plan = PanelKernelChoice();
+  ForEachPanel(k, [&](int first, int kp, int width) {
+    PanelUploadVectors(y, first, kp, width);
+    PanelTimer timer(&w, S(stream_));
+    PanelLaunchDots(plan, kp, width);
+    Check(milp_launch::panel_deinterleave(width, w.cols.get(), n_total_, kp, w.flat.get(),
+                                          n_total_, S(stream_)),
+          "panel de-interleave");
+    timer.Launched();
+    Download(out + size_t(first) * n_total_, w.flat.get(),
+             size_t(kp) * n_total_ * sizeof(double));
+    timer.Downloaded();
+    PanelRecord(plan, width, &w.last_panel);
+  });
+  DeviceOp("column dots panel done");
+}
+
+void DeviceLp::ColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
+                                     const uint64_t* keep_words, SparseRows* out) {
+  if (!shards_.empty()) {
+    return ShardedColumnDotsPanelSparse(y, k, drop_tolerance, keep_words, out);
+  }
+  PanelWorkspace& w = *panel_;
+  w.last_panel_sparse = LastPanelSparse();
+  out->row_starts.assign(size_t(std::max(k, 0)) + 1, 0);
+  out->cols.clear();
+  out->vals.clear();
+  if (k <= 0 || n_total_ <= 0) return;
+  DeviceOp("column dots panel sparse");
+  const PanelPlan plan = PanelKernelChoice();
+  const int tiles = (n_total_ + milp_kernels::kPanelTileColumns - 1) /
+                    milp_kernels::kPanelTileColumns;
+  const size_t mask_words = size_t((n_total_ + 63) / 64);
+  ForEachPanel(k, [&](int first, int kp, int width) {
+    PanelUploadVectors(y, first, kp, width);
+    PanelTimer timer(&w, S(stream_));
+    PanelLaunchDots(plan, kp, width);
+    // The sparse form's own buffers; `flat` takes the packed values.
+    w.kept_cols.Reserve(size_t(n_total_) * kp, "panel kept columns");
+    w.keep_mask.Reserve(mask_words, "panel mask");
+    w.counts.Reserve(size_t(kp) * tiles, "panel counts");
+    w.offsets.Reserve(size_t(kp) * tiles + milp_kernels::kPanelMaxWidth, "panel offsets");
+    const int64_t* totals = w.totals.Reserve(milp_kernels::kPanelMaxWidth, "panel totals");
+    if (first == 0 && keep_words != nullptr) {
+      Upload(w.keep_mask.get(), keep_words, mask_words * sizeof(uint64_t));
+    }
+    milp_kernels::PanelSparseArgs a{};
+    a.in = w.cols.get();
+    a.ncols = n_total_;
+    a.kp = kp;
+    a.tiles = tiles;
+    a.mask = keep_words != nullptr ? w.keep_mask.get() : nullptr;
+    a.drop_tolerance = drop_tolerance;
+    a.counts = w.counts.get();
+    a.offsets = w.offsets.get();
+    a.totals = w.offsets.get() + size_t(kp) * tiles;
+    a.cols = w.kept_cols.get();
+    a.vals = w.flat.get();
+    Check(milp_launch::panel_sparse(width, a, S(stream_)), "panel sparse rows");
+    timer.Launched();
+    // Down: the kp totals, then exactly the kept entries.
+    Download(w.totals.get(), a.totals, size_t(kp) * sizeof(int64_t));
+    int64_t kept = 0;
+    for (int v = 0; v < kp; ++v) {
+      if (totals[v] < 0 || totals[v] > n_total_) {
+        throw DeviceError("panel sparse rows: bad count");
+      }
+      kept += totals[v];
+      out->row_starts[first + v + 1] = out->row_starts[first + v] + totals[v];
+    }
+    const size_t old = out->cols.size();
+    out->cols.resize(old + size_t(kept));
+    out->vals.resize(old + size_t(kept));
+    if (kept > 0) {
+      Check(hipMemcpyAsync(out->cols.data() + old, a.cols, size_t(kept) * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+      Download(out->vals.data() + old, a.vals, size_t(kept) * sizeof(double));
+    }
+    timer.Downloaded();
+    PanelRecord(plan, width, &w.last_panel_sparse.panel);
+    w.last_panel_sparse.kept += kept;
+    w.last_panel_sparse.bytes_down += int64_t(kp) * 8 + kept * 12;
+  });
+  DeviceOp("column dots panel sparse done");
+}
+
+bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const int32_t* cols) {
+  if (k < 0 || starts[0] != 0) return false;
+  for (int j = 0; j < k; ++j) {
+    if (starts[j + 1] < starts[j]) return false;
+  }
+  if (starts[k] == 0) return true;
+  if (cols == nullptr) return false;
+  std::vector<int32_t> stamp(size_t(std::max(num_cols, 0)), 0);  // point + 1 that last set it
+  for (int j = 0; j < k; ++j) {
+    for (int64_t i = starts[j]; i < starts[j + 1]; ++i) {
+      const int32_t c = cols[i];
+      if (c < 0 || c >= num_cols || stamp[c] == j + 1) return false;
+      stamp[c] = j + 1;
+    }
+  }
+  return true;
+}
+
+// The interleaved points of one panel are in `cols`: the sums into `rows`,
+// vector-major into `flat`, down to out, and the record.
+void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer, double* out) {
+  PanelWorkspace& w = *panel_;
+  milp_kernels::RowPanelArgs a{};
+  a.t_starts = d_t_starts_;
+  a.t_cols = d_t_cols_;
+  a.t_vals = d_t_vals_;
+  a.x = w.cols.get();
+  a.num_rows = m_;
+  a.kp = kp;
+  a.out = w.rows.get();
+  Check(milp_launch::row_sums_panel(width, a, S(stream_)), "row sums panel");
+  Check(milp_launch::panel_deinterleave(width, w.rows.get(), m_, kp, w.flat.get(), m_,
+                                        S(stream_)),
+        "row panel de-interleave");
+  timer->Launched();
+  Download(out + size_t(first) * m_, w.flat.get(), size_t(kp) * m_ * sizeof(double));
+  timer->Downloaded();
+  w.last_row_panel.panels += 1;
+  w.last_row_panel.width = width;
+  w.last_row_panel.kernel = kRowPanelDirect;
+}
+
+void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
+  PanelWorkspace& w = *panel_;
+  w.last_row_panel = LastRowPanel();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("row sums panel");
+  ForEachPanel(k, [&](int first, int kp, int width) {
+    PanelReserve(width, kp);
+    Upload(w.flat.get(), x + size_t(first) * n_total_, size_t(kp) * n_total_ * sizeof(double));
+    PanelTimer timer(&w, S(stream_));
+    Check(milp_launch::panel_interleave(width, w.flat.get(), n_total_, n_total_, kp,
+                                        w.cols.get(), S(stream_)),
+          "row panel interleave");
+    RowPanelSums(first, kp, width, &timer, out);
+  });
+  DeviceOp("row sums panel done");
+}
+
+void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts,
+                                const int32_t* cols, const double* vals, double* out) {
+  PanelWorkspace& w = *panel_;
+  w.last_row_panel = LastRowPanel();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("row sums panel from");
+  const int64_t overrides = starts[k];
+  Upload(w.base.Reserve(size_t(n_total_), "panel base point"), base,
+         size_t(n_total_) * sizeof(double));
+  Upload(w.ov_starts.Reserve(size_t(k) + 1, "panel override starts"), starts,
+         (size_t(k) + 1) * sizeof(int64_t));
+  Upload(w.ov_cols.Reserve(size_t(overrides), "panel override columns"), cols,
+         size_t(overrides) * sizeof(int32_t));
+  Upload(w.ov_vals.Reserve(size_t(overrides), "panel override values"), vals,
+         size_t(overrides) * sizeof(double));
+  w.last_row_panel.overrides_up_bytes =
+      8 * int64_t(n_total_) + 12 * overrides + 8 * (int64_t(k) + 1);
+  ForEachPanel(k, [&](int first, int kp, int width) {
+    PanelReserve(width, kp);
+    PanelTimer timer(&w, S(stream_));
+    Check(milp_launch::panel_fill(width, w.base.get(), n_total_, kp, w.cols.get(), S(stream_)),
+          "row panel fill");
+    milp_kernels::RowPanelOverrideArgs o{};
+    o.starts = w.ov_starts.get() + first;
+    o.cols = w.ov_cols.get();
+    o.vals = w.ov_vals.get();
+    o.kp = kp;
+    o.x = w.cols.get();
+    Check(milp_launch::panel_override(width, o, starts[first + kp] - starts[first], S(stream_)),
+          "row panel overrides");
+    RowPanelSums(first, kp, width, &timer, out);
+  });
+  DeviceOp("row sums panel from done");
+}
+
+}  // namespace milp

@@ -32,6 +32,7 @@
 
 #include "../kernels/kernel_args.h"
 #include "device_lp.h"
+#include "device_panel.h"
 #include "lp_data.h"
 
 namespace milp {
@@ -422,7 +423,8 @@ void DeviceLp::ShardedPricing(const std::vector<double>& c, const std::vector<do
 // parts travel through ExchangeParts like every other join.
 void DeviceLp::ShardedColumnDotsPanel(const double* y, int k, double* out) {
   DeviceGuard guard{device_};
-  last_panel_ = LastPanel();
+  LastPanel& record = panel_->last_panel;
+  record = LastPanel();
   if (k <= 0) return;
   const int ns = num_shards();
   std::vector<std::string> parts(ns);
@@ -433,11 +435,7 @@ void DeviceLp::ShardedColumnDotsPanel(const double* y, int k, double* out) {
     part.assign(size_t(k) * d.n_total_, 0.0);
     if (d.n_total_ > 0) {
       d.ColumnDotsPanel(y, k, part.data());
-      const LastPanel p = d.last_panel();
-      last_panel_.sparse = std::max(last_panel_.sparse, p.sparse);
-      last_panel_.dense = last_panel_.dense || p.dense;
-      last_panel_.panels = p.panels;
-      last_panel_.width = p.width;
+      record.Merge(d.last_panel());
     }
     PartWriter w;
     w.Put(part);
@@ -463,7 +461,8 @@ void DeviceLp::ShardedColumnDotsPanel(const double* y, int k, double* out) {
 void DeviceLp::ShardedColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
                                             const uint64_t* keep_words, SparseRows* out) {
   DeviceGuard guard{device_};
-  last_panel_sparse_ = LastPanelSparse();
+  LastPanelSparse& record = panel_->last_panel_sparse;
+  record = LastPanelSparse();
   out->row_starts.assign(size_t(std::max(k, 0)) + 1, 0);
   out->cols.clear();
   out->vals.clear();
@@ -489,12 +488,9 @@ void DeviceLp::ShardedColumnDotsPanelSparse(const double* y, int k, double drop_
       d.ColumnDotsPanelSparse(y, k, drop_tolerance, keep_words != nullptr ? words.data() : nullptr,
                               &part);
       const LastPanelSparse p = d.last_panel_sparse();
-      last_panel_sparse_.panel.sparse = std::max(last_panel_sparse_.panel.sparse, p.panel.sparse);
-      last_panel_sparse_.panel.dense = last_panel_sparse_.panel.dense || p.panel.dense;
-      last_panel_sparse_.panel.panels = p.panel.panels;
-      last_panel_sparse_.panel.width = p.panel.width;
-      last_panel_sparse_.kept += p.kept;
-      last_panel_sparse_.bytes_down += p.bytes_down;
+      record.panel.Merge(p.panel);
+      record.kept += p.kept;
+      record.bytes_down += p.bytes_down;
     }
     PartWriter w;
     w.Put(part.row_starts);

@@ -6118,6 +6118,22 @@ bool SolveIsParked(const mi_lp* h) {
   std::lock_guard<std::mutex> l(m->mu);
   return !m->running || m->paused || m->finished;
 }
+
+// The device part of a panel entry point: `call` returns an MI_LP_* code with
+// the handle's device current; what it throws becomes a code and h->error.
+template <typename Call>
+int PanelCall(mi_lp* h, Call call) {
+  try {
+    (void)hipSetDevice(h->device);
+    return call();
+  } catch (const milp::DeviceError& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+}
 }  // namespace
 
 extern "C" {
@@ -6229,60 +6245,25 @@ int mi_lp_get_unit_row_left_inverse(mi_lp* h, int32_t row, double* values, int32
   return MI_LP_OK;
 }
 
-int mi_lp_row_combinations(mi_lp* h, const double* y, int32_t k, double* out) {
-  if (h == nullptr || y == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
-  if (!h->solved) return MI_LP_ERROR_STATE;
-  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
-  if (k == 0) return MI_LP_OK;
-  try {
-    (void)hipSetDevice(h->device);
-    h->simplex.device().ColumnDotsPanel(y, k, out);
-  } catch (const milp::DeviceError& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_DEVICE;
-  } catch (const std::exception& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_INTERNAL;
-  }
-  return MI_LP_OK;
-}
-
-int mi_lp_get_tableau_rows(mi_lp* h, const int32_t* rows, int32_t k, double* out,
-                           double* left_inverses) {
-  if (h == nullptr || rows == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
-  if (!h->solved) return MI_LP_ERROR_STATE;
-  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
-  const int m = h->lp.m;
-  for (int32_t j = 0; j < k; ++j) {
-    if (rows[j] < 0 || rows[j] >= m) return MI_LP_ERROR_INVALID_PROBLEM;
-  }
-  if (k == 0) return MI_LP_OK;
-  try {
-    (void)hipSetDevice(h->device);
-    // The k left solves stay on the host, one GetUnitRowLeftInverse each, in
-    // the caller's order; only the products with [A | I] are batched.
-    std::vector<double> local;
-    double* y = left_inverses;
-    if (y == nullptr) {
-      local.resize(size_t(k) * m);
-      y = local.data();
-    }
-    for (int32_t j = 0; j < k; ++j) {
-      const milp::ScatteredVector& v = h->simplex.GetUnitRowLeftInverse(rows[j]);
-      for (int r = 0; r < m; ++r) y[size_t(j) * m + r] = v.values[r];
-    }
-    h->simplex.device().ColumnDotsPanel(y, k, out);
-  } catch (const milp::DeviceError& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_DEVICE;
-  } catch (const std::exception& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_INTERNAL;
-  }
-  return MI_LP_OK;
-}
-
 namespace {
+// The left inverses of rows[0 .. k) as k x m, in the caller's buffer or in
+// *local: k host left solves, one GetUnitRowLeftInverse each, in the caller's
+// order (only the products with [A | I] are batched).
+const double* LeftInverses(mi_lp* h, const int32_t* rows, int32_t k, double* left_inverses,
+                           std::vector<double>* local) {
+  const int m = h->lp.m;
+  double* y = left_inverses;
+  if (y == nullptr) {
+    local->resize(std::max<size_t>(1, size_t(k) * m));
+    y = local->data();
+  }
+  for (int32_t j = 0; j < k; ++j) {
+    const milp::ScatteredVector& v = h->simplex.GetUnitRowLeftInverse(rows[j]);
+    for (int r = 0; r < m; ++r) y[size_t(j) * m + r] = v.values[r];
+  }
+  return y;
+}
+
 // The argument checks the two sparse calls share; MI_LP_OK when they pass.
 int CheckSparseRowArgs(const mi_lp* h, int32_t k, double drop_tolerance, uint32_t column_filter) {
   if (!h->solved) return MI_LP_ERROR_STATE;
@@ -6322,22 +6303,42 @@ void StoreSparseRows(mi_lp* h, const double* y, int32_t k, double drop_tolerance
 }
 }  // namespace
 
+int mi_lp_row_combinations(mi_lp* h, const double* y, int32_t k, double* out) {
+  if (h == nullptr || y == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&] {
+    h->simplex.device().ColumnDotsPanel(y, k, out);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_get_tableau_rows(mi_lp* h, const int32_t* rows, int32_t k, double* out,
+                           double* left_inverses) {
+  if (h == nullptr || rows == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  for (int32_t j = 0; j < k; ++j) {
+    if (rows[j] < 0 || rows[j] >= h->lp.m) return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&] {
+    std::vector<double> local;
+    h->simplex.device().ColumnDotsPanel(LeftInverses(h, rows, k, left_inverses, &local), k, out);
+    return MI_LP_OK;
+  });
+}
+
 int mi_lp_row_combinations_sparse(mi_lp* h, const double* y, int32_t k, double drop_tolerance,
                                   uint32_t column_filter, int64_t* row_starts) {
   if (h == nullptr || y == nullptr || row_starts == nullptr) return MI_LP_ERROR_NULL;
   const int bad = CheckSparseRowArgs(h, k, drop_tolerance, column_filter);
   if (bad != MI_LP_OK) return bad;
-  try {
-    (void)hipSetDevice(h->device);
+  return PanelCall(h, [&] {
     StoreSparseRows(h, y, k, drop_tolerance, column_filter, row_starts);
-  } catch (const milp::DeviceError& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_DEVICE;
-  } catch (const std::exception& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_INTERNAL;
-  }
-  return MI_LP_OK;
+    return MI_LP_OK;
+  });
 }
 
 int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
@@ -6346,32 +6347,15 @@ int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
   if (h == nullptr || rows == nullptr || row_starts == nullptr) return MI_LP_ERROR_NULL;
   const int bad = CheckSparseRowArgs(h, k, drop_tolerance, column_filter);
   if (bad != MI_LP_OK) return bad;
-  const int m = h->lp.m;
   for (int32_t j = 0; j < k; ++j) {
-    if (rows[j] < 0 || rows[j] >= m) return MI_LP_ERROR_INVALID_PROBLEM;
+    if (rows[j] < 0 || rows[j] >= h->lp.m) return MI_LP_ERROR_INVALID_PROBLEM;
   }
-  try {
-    (void)hipSetDevice(h->device);
-    // As mi_lp_get_tableau_rows: k host left solves in the caller's order.
+  return PanelCall(h, [&] {
     std::vector<double> local;
-    double* y = left_inverses;
-    if (y == nullptr) {
-      local.resize(std::max<size_t>(1, size_t(k) * m));
-      y = local.data();
-    }
-    for (int32_t j = 0; j < k; ++j) {
-      const milp::ScatteredVector& v = h->simplex.GetUnitRowLeftInverse(rows[j]);
-      for (int r = 0; r < m; ++r) y[size_t(j) * m + r] = v.values[r];
-    }
-    StoreSparseRows(h, y, k, drop_tolerance, column_filter, row_starts);
-  } catch (const milp::DeviceError& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_DEVICE;
-  } catch (const std::exception& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_INTERNAL;
-  }
-  return MI_LP_OK;
+    StoreSparseRows(h, LeftInverses(h, rows, k, left_inverses, &local), k, drop_tolerance,
+                    column_filter, row_starts);
+    return MI_LP_OK;
+  });
 }
 
 int mi_lp_column_combinations(mi_lp* h, const double* x, int32_t k, double* out) {
@@ -6379,17 +6363,10 @@ int mi_lp_column_combinations(mi_lp* h, const double* x, int32_t k, double* out)
   if (!h->solved) return MI_LP_ERROR_STATE;
   if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
   if (k == 0) return MI_LP_OK;
-  try {
-    (void)hipSetDevice(h->device);
+  return PanelCall(h, [&] {
     h->simplex.device().RowSumsPanel(x, k, out);
-  } catch (const milp::DeviceError& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_DEVICE;
-  } catch (const std::exception& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_INTERNAL;
-  }
-  return MI_LP_OK;
+    return MI_LP_OK;
+  });
 }
 
 int mi_lp_column_combinations_from(mi_lp* h, const double* base, int32_t k,
@@ -6401,7 +6378,7 @@ int mi_lp_column_combinations_from(mi_lp* h, const double* base, int32_t k,
   if (!h->solved) return MI_LP_ERROR_STATE;
   if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
   if (k == 0) return MI_LP_OK;
-  try {
+  return PanelCall(h, [&]() -> int {
     // starts first: starts[k] is read only once the entries before it are
     // known to ascend from 0.
     if (starts[0] != 0) return MI_LP_ERROR_INVALID_PROBLEM;
@@ -6412,16 +6389,9 @@ int mi_lp_column_combinations_from(mi_lp* h, const double* base, int32_t k,
     if (!milp::DeviceLp::ValidOverrides(h->lp.n + h->lp.m, k, starts, cols)) {
       return MI_LP_ERROR_INVALID_PROBLEM;
     }
-    (void)hipSetDevice(h->device);
     h->simplex.device().RowSumsPanelFrom(base, k, starts, cols, vals, out);
-  } catch (const milp::DeviceError& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_DEVICE;
-  } catch (const std::exception& e) {
-    h->error = e.what();
-    return MI_LP_ERROR_INTERNAL;
-  }
-  return MI_LP_OK;
+    return MI_LP_OK;
+  });
 }
 
 int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals) {

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "block_scan.h"
 #include "kernel_args.h"
 
@@ -456,94 +458,79 @@ using namespace milp_kernels;
 
 static inline int panel_div_up(long a, long b) { return static_cast<int>((a + b - 1) / b); }
 
-hipError_t column_dot_panel(int width, bool long_columns, const PanelDotArgs& args,
-                            hipStream_t s) {
-  if (args.ncols <= 0) return hipSuccess;
-  if (long_columns) {
-    switch (width) {
-      case 1: column_dot_panel_long_kernel<1><<<args.ncols, 64, 0, s>>>(args); break;
-      case 4: column_dot_panel_long_kernel<4><<<args.ncols, 64, 0, s>>>(args); break;
-      case 16: column_dot_panel_long_kernel<16><<<args.ncols, 64, 0, s>>>(args); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  const int blocks = panel_div_up(args.ncols, 256 / (4 * width));
+// launch(std::integral_constant<int, K>) for the panel width K = width, then
+// the launch error. A width other than 1, 4 or 16 launches nothing.
+template <typename Launch>
+static hipError_t for_panel_width(int width, Launch launch) {
   switch (width) {
-    case 1: column_dot_panel_short_kernel<1><<<blocks, 256, 0, s>>>(args); break;
-    case 4: column_dot_panel_short_kernel<4><<<blocks, 256, 0, s>>>(args); break;
-    case 16: column_dot_panel_short_kernel<16><<<blocks, 256, 0, s>>>(args); break;
+    case 1: launch(std::integral_constant<int, 1>()); break;
+    case 4: launch(std::integral_constant<int, 4>()); break;
+    case 16: launch(std::integral_constant<int, 16>()); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
 }
 
+hipError_t column_dot_panel(int width, bool long_columns, const PanelDotArgs& args,
+                            hipStream_t s) {
+  if (args.ncols <= 0) return hipSuccess;
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    if (long_columns) {
+      column_dot_panel_long_kernel<K><<<args.ncols, 64, 0, s>>>(args);
+    } else {
+      const int blocks = panel_div_up(args.ncols, 256 / (4 * K));
+      column_dot_panel_short_kernel<K><<<blocks, 256, 0, s>>>(args);
+    }
+  });
+}
+
 hipError_t dense_dot_panel(int width, const PanelDenseArgs& args, hipStream_t s) {
   if (args.nd <= 0) return hipSuccess;
   const int blocks = panel_div_up(args.nd, kDenseColsPerBlock);
-  switch (width) {
-    case 1: dense_dot_panel_kernel<1, 8><<<blocks, 256, 0, s>>>(args); break;
-    case 4: dense_dot_panel_kernel<4, 8><<<blocks, 256, 0, s>>>(args); break;
-    case 16: dense_dot_panel_kernel<16, 4><<<blocks, 256, 0, s>>>(args); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    constexpr int kUnroll = K == 16 ? 4 : 8;
+    dense_dot_panel_kernel<K, kUnroll><<<blocks, 256, 0, s>>>(args);
+  });
 }
 
 hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, double* out,
                               int64_t ld, hipStream_t s) {
   if (ncols <= 0 || kp <= 0) return hipSuccess;
   const int blocks = panel_div_up(ncols, 64);
-  switch (width) {
-    case 1: deinterleave_kernel<1><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
-    case 4: deinterleave_kernel<4><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
-    case 16: deinterleave_kernel<16><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return for_panel_width(width, [&](auto w) {
+    deinterleave_kernel<decltype(w)::value><<<blocks, 256, 0, s>>>(in, ncols, kp, out, ld);
+  });
 }
 
 hipError_t panel_sparse(int width, const PanelSparseArgs& args, hipStream_t s) {
   if (args.ncols <= 0 || args.kp <= 0) return hipSuccess;
   if (args.tiles != panel_div_up(args.ncols, kPanelTileColumns)) return hipErrorInvalidValue;
-  switch (width) {
-    case 1: panel_count_kernel<1><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
-    case 4: panel_count_kernel<4><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
-    case 16: panel_count_kernel<16><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
-    default: return hipErrorInvalidValue;
-  }
-  panel_offsets_kernel<<<1, kPanelOffsetsStep, 0, s>>>(args);
-  switch (width) {
-    case 1: panel_write_kernel<1><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
-    case 4: panel_write_kernel<4><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
-    default: panel_write_kernel<16><<<args.tiles, kPanelTileColumns, 0, s>>>(args); break;
-  }
-  return hipGetLastError();
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    panel_count_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+    panel_offsets_kernel<<<1, kPanelOffsetsStep, 0, s>>>(args);
+    panel_write_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+  });
 }
 
 hipError_t row_sums_panel(int width, const RowPanelArgs& args, hipStream_t s) {
   if (args.num_rows <= 0 || args.kp <= 0) return hipSuccess;
-  if (width != 1 && width != 4 && width != 16) return hipErrorInvalidValue;
-  const int blocks = panel_div_up(args.num_rows, kRowPanelThreads / width);
-  switch (width) {
-    case 1: row_sums_panel_kernel<1><<<blocks, kRowPanelThreads, 0, s>>>(args); break;
-    case 4: row_sums_panel_kernel<4><<<blocks, kRowPanelThreads, 0, s>>>(args); break;
-    default: row_sums_panel_kernel<16><<<blocks, kRowPanelThreads, 0, s>>>(args); break;
-  }
-  return hipGetLastError();
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    const int blocks = panel_div_up(args.num_rows, kRowPanelThreads / K);
+    row_sums_panel_kernel<K><<<blocks, kRowPanelThreads, 0, s>>>(args);
+  });
 }
 
 hipError_t panel_interleave(int width, const double* in, int64_t ld, int ncols, int kp,
                             double* out, hipStream_t s) {
   if (ncols <= 0) return hipSuccess;
   const int blocks = panel_div_up(ncols, 64);
-  switch (width) {
-    case 1: interleave_kernel<1><<<blocks, 256, 0, s>>>(in, ld, ncols, kp, out); break;
-    case 4: interleave_kernel<4><<<blocks, 256, 0, s>>>(in, ld, ncols, kp, out); break;
-    case 16: interleave_kernel<16><<<blocks, 256, 0, s>>>(in, ld, ncols, kp, out); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return for_panel_width(width, [&](auto w) {
+    interleave_kernel<decltype(w)::value><<<blocks, 256, 0, s>>>(in, ld, ncols, kp, out);
+  });
 }
 
 // Grid-stride kernels: at most 2048 workgroups.
@@ -555,27 +542,20 @@ static inline int panel_stride_blocks(int64_t elements) {
 hipError_t panel_fill(int width, const double* base, int ncols, int kp, double* out,
                       hipStream_t s) {
   if (ncols <= 0) return hipSuccess;
-  const int blocks = panel_stride_blocks(static_cast<int64_t>(ncols) * width);
-  switch (width) {
-    case 1: panel_fill_kernel<1><<<blocks, 256, 0, s>>>(base, ncols, kp, out); break;
-    case 4: panel_fill_kernel<4><<<blocks, 256, 0, s>>>(base, ncols, kp, out); break;
-    case 16: panel_fill_kernel<16><<<blocks, 256, 0, s>>>(base, ncols, kp, out); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    const int blocks = panel_stride_blocks(static_cast<int64_t>(ncols) * K);
+    panel_fill_kernel<K><<<blocks, 256, 0, s>>>(base, ncols, kp, out);
+  });
 }
 
 hipError_t panel_override(int width, const RowPanelOverrideArgs& args, int64_t num_overrides,
                           hipStream_t s) {
   if (num_overrides <= 0 || args.kp <= 0) return hipSuccess;
   const int blocks = panel_stride_blocks(num_overrides);
-  switch (width) {
-    case 1: panel_override_kernel<1><<<blocks, 256, 0, s>>>(args); break;
-    case 4: panel_override_kernel<4><<<blocks, 256, 0, s>>>(args); break;
-    case 16: panel_override_kernel<16><<<blocks, 256, 0, s>>>(args); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return for_panel_width(width, [&](auto w) {
+    panel_override_kernel<decltype(w)::value><<<blocks, 256, 0, s>>>(args);
+  });
 }
 
 }  // namespace milp_launch
