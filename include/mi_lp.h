@@ -365,6 +365,74 @@ int mi_lp_column_combinations_from(mi_lp* h, const double* base, int32_t k,
                                    const int64_t* starts, const int32_t* cols,
                                    const double* vals, double* out);
 
+/* The same activities filtered on the GPU: per point the rows outside their
+ * bounds and a 24-byte summary, so that the download is proportional to what
+ * is violated and not to k m. With a the value that is bit for bit
+ * out[j m + r] of mi_lp_column_combinations on the same point (for the
+ * override form: on the materialised points), lo = row_lb[r], hi = row_ub[r]
+ * and tol = tolerance, where lo - tol and hi + tol are one rounded double
+ * operation each:
+ *   violated     row r is violated at point j iff
+ *                !(a >= lo - tol) || !(a <= hi + tol). Strict towards
+ *                feasibility: an activity exactly on a widened bound is not
+ *                violated, one ulp outside it is; a NaN activity is always
+ *                violated; +-inf activities follow the comparisons.
+ *   amount       of a violated row: +inf when a is NaN, otherwise the larger
+ *                of lo - a and a - hi, each rounded once. With the argument
+ *                checks below neither difference is NaN for a non-NaN a of a
+ *                violated row, and every amount is > 0.
+ *   lists        row_starts has k+1 entries, row_starts[k] is the entry
+ *                count. Point j's entries are its violated rows in strictly
+ *                increasing row order, each with a's bits as its activity.
+ *   summaries    one per point: count is the number of violated rows, worst
+ *                the largest amount (0.0 when count == 0), worst_row the
+ *                lowest row whose amount equals worst (-1 when count == 0),
+ *                reserved 0. An integer sum, an exact maximum and a minimum
+ *                index: the same bits whatever order the GPU reduces in. A
+ *                sum of the amounts is not offered (it would need a fixed
+ *                summation order to be reproducible).
+ * Two calls, as the sparse rows above:
+ *   mi_lp_column_combinations_violations       compute, store the lists in the handle and
+ *   mi_lp_column_combinations_from_violations  write row_starts and summaries;
+ *   mi_lp_get_violated_rows                    copies the stored rows and activities out,
+ *                                              row_starts[k] of each.
+ * x, base, starts, cols and vals are those of the dense calls: the points are
+ * over all n+m columns of [A | I], so a caller who wants plain A x passes
+ * zero slack entries. row_lb / row_ub hold m entries each; either may be NULL
+ * and then means the bounds given to mi_lp_load. summaries may be NULL.
+ * row_starts may be NULL and means summaries only: no list is built,
+ * downloaded or stored, and a previously stored list stays. Both NULL:
+ * MI_LP_ERROR_NULL. The stored list is the handle's own, separate from the
+ * sparse rows' (mi_lp_get_sparse_rows and the sparse-row calls neither see
+ * nor disturb it, nor the other way round); it lives until the next
+ * violations call that builds lists, mi_lp_load or mi_lp_destroy.
+ * Errors, with nothing written and the stored list untouched:
+ * MI_LP_ERROR_INVALID_PROBLEM for k < 0, a tolerance that is negative, NaN
+ * or infinite, a NaN bound, row_lb[r] == +inf or row_ub[r] == -inf (lb > ub
+ * is allowed: such a row is violated at every point), and, for the override
+ * form, every condition of mi_lp_column_combinations_from. MI_LP_ERROR_NULL:
+ * NULL pointers as in the dense calls. MI_LP_ERROR_STATE: before a solve;
+ * mi_lp_get_violated_rows before any list-building call, or after
+ * mi_lp_load. k = 0 succeeds, writes row_starts[0] = 0 if row_starts is
+ * given and stores an empty list. Changes no state a later solve reads. */
+typedef struct mi_lp_point_violations {
+  int64_t count;
+  double worst;
+  int32_t worst_row;
+  int32_t reserved;
+} mi_lp_point_violations;
+int mi_lp_column_combinations_violations(mi_lp* h, const double* x, int32_t k,
+                                         const double* row_lb, const double* row_ub,
+                                         double tolerance, int64_t* row_starts,
+                                         mi_lp_point_violations* summaries);
+int mi_lp_column_combinations_from_violations(mi_lp* h, const double* base, int32_t k,
+                                              const int64_t* starts, const int32_t* cols,
+                                              const double* vals, const double* row_lb,
+                                              const double* row_ub, double tolerance,
+                                              int64_t* row_starts,
+                                              mi_lp_point_violations* summaries);
+int mi_lp_get_violated_rows(const mi_lp* h, int32_t* rows, double* activities);
+
 /* interrupt may be NULL; a non-zero value stops the solve like a time limit
  * (glop_interface.cc:138-140). */
 int mi_lp_solve(mi_lp* h, const volatile int32_t* interrupt, mi_lp_result* out);

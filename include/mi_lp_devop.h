@@ -109,6 +109,25 @@ typedef struct mi_devop_row_panel_geometry {
   int32_t chunk;                 /* staging chunk length; 0: the kernel does not stage */
 } mi_devop_row_panel_geometry;
 
+/* mi_lp_point_violations of include/mi_lp.h, restated so that this header
+ * stands alone. */
+typedef struct mi_devop_point_violations {
+  int64_t count;
+  double worst;
+  int32_t worst_row; /* -1 when count == 0 */
+  int32_t reserved;
+} mi_devop_point_violations;
+/* DeviceLp::LastRowViolations: the last row_violations_panel(_from). */
+typedef struct mi_devop_row_violations {
+  int32_t panels;             /* panels of up to 16 points */
+  int32_t width;              /* padded width of the last panel: 1, 4 or 16 */
+  int32_t lists;              /* lists were built (row_starts given) */
+  int32_t reserved;
+  int64_t kept;               /* entries of all points */
+  int64_t bytes_down;         /* device-to-host bytes of the call */
+  int64_t overrides_up_bytes; /* host-to-device bytes of a row_violations_panel_from call */
+} mi_devop_row_violations;
+
 typedef struct mi_devop_api {
   /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
   mi_devop* (*create)(int device, int m, int n, const int64_t* col_starts,
@@ -190,6 +209,26 @@ typedef struct mi_devop_api {
                              const int32_t* cols, const double* vals, double* out);
   int (*last_row_panel)(mi_devop* h, mi_devop_row_panel* out);
   int (*row_panel_geometry)(mi_devop_row_panel_geometry* out);
+  /* Appended after row_panel_geometry. DeviceLp::RowViolationsPanel in one
+   * call (the rule: include/mi_lp.h mi_lp_column_combinations_violations). x:
+   * k x N; row_lb / row_ub: m each, not NULL, no NaN, row_lb < +inf and
+   * row_ub > -inf; tolerance finite and >= 0 (checked here). row_starts:
+   * k + 1; rows / activities: `capacity` entries; summaries: k, or NULL.
+   * row_starts == NULL selects summaries only: rows and activities are not
+   * touched. A result of more than `capacity` entries returns
+   * MI_DEVOP_CAPACITY (last_error says how many) with row_starts, rows,
+   * activities and summaries unwritten; it is no device error. */
+  int (*row_violations_panel)(mi_devop* h, const double* x, int k, const double* row_lb,
+                              const double* row_ub, double tolerance, int64_t* row_starts,
+                              int32_t* rows, double* activities, int64_t capacity,
+                              mi_devop_point_violations* summaries);
+  /* base, starts, cols, vals and their checks as row_sums_panel_from. */
+  int (*row_violations_panel_from)(mi_devop* h, const double* base, int k, const int64_t* starts,
+                                   const int32_t* cols, const double* vals, const double* row_lb,
+                                   const double* row_ub, double tolerance, int64_t* row_starts,
+                                   int32_t* rows, double* activities, int64_t capacity,
+                                   mi_devop_point_violations* summaries);
+  int (*last_row_violations)(mi_devop* h, mi_devop_row_violations* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

@@ -253,6 +253,43 @@ class DeviceLp : public DeviceSolver {
   // its staging chunk length (0: it reads the rows directly), for the tests.
   static void RowPanelGeometry(int rows_per_workgroup[3], int* chunk);
 
+  // The same row sums filtered on the device (include/mi_lp.h
+  // mi_lp_column_combinations_violations has the rule): per point the rows
+  // with !(a >= row_lb - tolerance) || !(a <= row_ub + tolerance), ascending,
+  // with a's bits, and one summary per point. The points are built and the
+  // sums launched exactly as RowSumsPanel / RowSumsPanelFrom do (one code
+  // path); then violations_count / panel_offsets / violations_fold /
+  // violations_write work on the interleaved sums, and per panel only the kp
+  // totals (lists), the kp summaries (summaries) and the kept (4-byte row,
+  // 8-byte activity) entries come down. row_lb / row_ub: m values, host; the
+  // widened bounds are formed in the kernels. lists == false: no offsets, no
+  // write pass, no entries (out's list members are left empty); summaries ==
+  // false: no fold. Panels are appended point-major. With column shards it
+  // stays on the unsplit handle, as RowSumsPanel does; last_row_panel() is
+  // not changed. Synchronizes before it returns.
+  struct RowViolations {
+    std::vector<int64_t> row_starts;  // k + 1 (lists)
+    std::vector<int32_t> rows;        // row_starts[k]
+    std::vector<double> activities;
+    std::vector<mi_lp_point_violations> summaries;  // k (summaries)
+  };
+  void RowViolationsPanel(const double* x, int k, const double* row_lb, const double* row_ub,
+                          double tolerance, bool lists, bool summaries, RowViolations* out);
+  void RowViolationsPanelFrom(const double* base, int k, const int64_t* starts,
+                              const int32_t* cols, const double* vals, const double* row_lb,
+                              const double* row_ub, double tolerance, bool lists, bool summaries,
+                              RowViolations* out);
+  // The last RowViolationsPanel / RowViolationsPanelFrom (test record).
+  struct LastRowViolations {
+    int panels = 0;
+    int width = 0;                   // of the last panel
+    bool lists = false;              // lists were built
+    int64_t kept = 0;                // entries of all points
+    int64_t bytes_down = 0;          // device-to-host bytes of the call
+    int64_t overrides_up_bytes = 0;  // as LastRowPanel, of a RowViolationsPanelFrom call
+  };
+  LastRowViolations last_row_violations() const;
+
   // --- dual device mode: device-resident reduced costs ------------------
   // (see simplex.cc RevisedSimplex::DualDeviceMode). colbits: one byte per
   // column (kernel_args.h kCol*), bound_diff: upper - lower per column.
@@ -502,7 +539,26 @@ class DeviceLp : public DeviceSolver {
   void PanelUploadVectors(const double* y, int first, int kp, int width);
   void PanelLaunchDots(const PanelPlan& plan, int kp, int width);
   void PanelRecord(const PanelPlan& plan, int width, LastPanel* record) const;
-  void RowPanelSums(int first, int kp, int width, PanelTimer* timer, double* out);
+  // What a row-sum call does with each panel's interleaved sums: the dense
+  // form brings them down, the violations form filters them first.
+  struct RowPanelSink {
+    double* sums = nullptr;               // RowSumsPanel(From): k x m on the host
+    RowViolations* violations = nullptr;  // RowViolationsPanel(From)
+    double tolerance = 0.0;
+    bool lists = false;
+    bool summaries = false;
+  };
+  void RowPanels(const double* x, int k, const RowPanelSink& sink);
+  // Returns the bytes that went up once for the call.
+  int64_t RowPanelsFrom(const double* base, int k, const int64_t* starts, const int32_t* cols,
+                        const double* vals, const RowPanelSink& sink);
+  void RowPanelSums(int first, int kp, int width, PanelTimer* timer, const RowPanelSink& sink);
+  void RowPanelViolations(int first, int kp, int width, PanelTimer* timer,
+                          const RowPanelSink& sink);
+  // Resets the record and `out`, uploads the bounds; false when there is
+  // nothing to launch (k <= 0 or no rows).
+  bool RowViolationsBegin(int k, const double* row_lb, const double* row_ub, bool lists,
+                          bool summaries, RowViolations* out);
   bool is_shard_ = false;
   std::vector<std::unique_ptr<DeviceLp>> shards_;  // null: a block owned by another process
   ExchangeFn exchange_fn_ = nullptr;

@@ -1,7 +1,8 @@
 // The workspace of DeviceLp's panel calls (device_panel.hip): the buffers of
-// ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel and RowSumsPanelFrom,
-// their timing events and their test records. Included by the HIP translation
-// units only; device_lp.h holds the workspace behind a pointer.
+// ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel, RowSumsPanelFrom and
+// RowViolationsPanel(From), their timing events and their test records.
+// Included by the HIP translation units only; device_lp.h holds the workspace
+// behind a pointer.
 #ifndef MILP_DEVICE_PANEL_H_
 #define MILP_DEVICE_PANEL_H_
 
@@ -11,6 +12,7 @@
 #include <cstdint>
 #include <string>
 
+#include "../kernels/kernel_args.h"
 #include "device_lp.h"
 
 namespace milp {
@@ -79,17 +81,28 @@ struct PanelWorkspace {
   //   flat: vector-major, kp N        the results on their way      the points on their way
   //                                   down (sparse form: the        up, then the results
   //                                   packed kept values)           (kp m) on their way down
+  // The row violations (RowViolationsPanel, RowViolationsPanelFrom) are row
+  // sums up to the results in `rows`; then `flat` takes the packed kept
+  // activities (at most kp m <= kp N), the points having left it.
   DeviceBuffer<double> rows, cols, flat;
   PinnedBuffer<double> y_staging;  // column dots: the host interleave of y, max(1, m width)
 
-  // ColumnDotsPanelSparse.
-  DeviceBuffer<int32_t> kept_cols;   // packed kept columns, N kp
-  DeviceBuffer<uint64_t> keep_mask;  // ceil(N / 64) words
+  // ColumnDotsPanelSparse and the row violations: tiles of 256 columns
+  // (sparse rows) or 256 rows (violations).
+  DeviceBuffer<int32_t> kept_cols;   // packed kept columns, N kp / kept rows, at most m kp
+  DeviceBuffer<uint64_t> keep_mask;  // ceil(N / 64) words (sparse rows only)
   DeviceBuffer<int> counts;          // kp x tiles
   DeviceBuffer<int64_t> offsets;     // kp x tiles, then kPanelMaxWidth totals
   PinnedBuffer<int64_t> totals;      // kPanelMaxWidth
 
-  // RowSumsPanelFrom, uploaded once per call.
+  // The row violations only.
+  DeviceBuffer<double> row_lb, row_ub;    // the bounds, m each, uploaded once per call
+  DeviceBuffer<double> tile_worst;        // kp x tiles: largest amount of (point, tile)
+  DeviceBuffer<int32_t> tile_worst_row;   // kp x tiles: lowest row attaining it
+  DeviceBuffer<milp_kernels::PointViolations> summaries;       // kPanelMaxWidth
+  PinnedBuffer<milp_kernels::PointViolations> summaries_host;  // kPanelMaxWidth
+
+  // RowSumsPanelFrom and RowViolationsPanelFrom, uploaded once per call.
   DeviceBuffer<double> base;        // the base point, N
   DeviceBuffer<int64_t> ov_starts;  // k + 1
   DeviceBuffer<int32_t> ov_cols;    // overrides of the whole call
@@ -103,6 +116,7 @@ struct PanelWorkspace {
   DeviceLp::LastPanel last_panel;
   DeviceLp::LastPanelSparse last_panel_sparse;
   DeviceLp::LastRowPanel last_row_panel;
+  DeviceLp::LastRowViolations last_row_violations;
 };
 
 }  // namespace milp

@@ -1,11 +1,13 @@
 // DeviceLp's panel calls: k vectors per pass over [A | I] (see device_lp.h).
-// Column dots (ColumnDotsPanel, ColumnDotsPanelSparse) and row sums
-// (RowSumsPanel, RowSumsPanelFrom) share one workspace (device_panel.h), one
-// panel loop and one timing scope. No solve calls them and nothing a solve
+// Column dots (ColumnDotsPanel, ColumnDotsPanelSparse), row sums (RowSumsPanel,
+// RowSumsPanelFrom) and their violated rows (RowViolationsPanel,
+// RowViolationsPanelFrom) share one workspace (device_panel.h), one panel
+// loop and one timing scope. No solve calls them and nothing a solve
 // reads is written.
 #include "device_panel.h"
 
 #include <algorithm>
+#include <cstddef>
 #include <vector>
 
 #include "../kernels/kernel_args.h"
@@ -264,9 +266,11 @@ bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const 
   return true;
 }
 
-// The interleaved points of one panel are in `cols`: the sums into `rows`,
-// vector-major into `flat`, down to out, and the record.
-void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer, double* out) {
+// The interleaved points of one panel are in `cols`: the sums into `rows`;
+// then the dense form (vector-major into `flat`, down to sink.sums, and the
+// record) or the violations form.
+void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer,
+                            const RowPanelSink& sink) {
   PanelWorkspace& w = *panel_;
   milp_kernels::RowPanelArgs a{};
   a.t_starts = d_t_starts_;
@@ -277,22 +281,22 @@ void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer, dou
   a.kp = kp;
   a.out = w.rows.get();
   Check(milp_launch::row_sums_panel(width, a, S(stream_)), "row sums panel");
+  if (sink.violations != nullptr) return RowPanelViolations(first, kp, width, timer, sink);
   Check(milp_launch::panel_deinterleave(width, w.rows.get(), m_, kp, w.flat.get(), m_,
                                         S(stream_)),
         "row panel de-interleave");
   timer->Launched();
-  Download(out + size_t(first) * m_, w.flat.get(), size_t(kp) * m_ * sizeof(double));
+  Download(sink.sums + size_t(first) * m_, w.flat.get(), size_t(kp) * m_ * sizeof(double));
   timer->Downloaded();
   w.last_row_panel.panels += 1;
   w.last_row_panel.width = width;
   w.last_row_panel.kernel = kRowPanelDirect;
 }
 
-void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
+// The k dense points, panel by panel: up vector-major, interleaved on the
+// device, then RowPanelSums.
+void DeviceLp::RowPanels(const double* x, int k, const RowPanelSink& sink) {
   PanelWorkspace& w = *panel_;
-  w.last_row_panel = LastRowPanel();
-  if (k <= 0 || m_ <= 0) return;
-  DeviceOp("row sums panel");
   ForEachPanel(k, [&](int first, int kp, int width) {
     PanelReserve(width, kp);
     Upload(w.flat.get(), x + size_t(first) * n_total_, size_t(kp) * n_total_ * sizeof(double));
@@ -300,17 +304,16 @@ void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
     Check(milp_launch::panel_interleave(width, w.flat.get(), n_total_, n_total_, kp,
                                         w.cols.get(), S(stream_)),
           "row panel interleave");
-    RowPanelSums(first, kp, width, &timer, out);
+    RowPanelSums(first, kp, width, &timer, sink);
   });
-  DeviceOp("row sums panel done");
 }
 
-void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts,
-                                const int32_t* cols, const double* vals, double* out) {
+// The k points base + overrides: base and the lists go up once, every panel
+// is filled and overridden on the device, then RowPanelSums.
+int64_t DeviceLp::RowPanelsFrom(const double* base, int k, const int64_t* starts,
+                                const int32_t* cols, const double* vals,
+                                const RowPanelSink& sink) {
   PanelWorkspace& w = *panel_;
-  w.last_row_panel = LastRowPanel();
-  if (k <= 0 || m_ <= 0) return;
-  DeviceOp("row sums panel from");
   const int64_t overrides = starts[k];
   Upload(w.base.Reserve(size_t(n_total_), "panel base point"), base,
          size_t(n_total_) * sizeof(double));
@@ -320,8 +323,6 @@ void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts
          size_t(overrides) * sizeof(int32_t));
   Upload(w.ov_vals.Reserve(size_t(overrides), "panel override values"), vals,
          size_t(overrides) * sizeof(double));
-  w.last_row_panel.overrides_up_bytes =
-      8 * int64_t(n_total_) + 12 * overrides + 8 * (int64_t(k) + 1);
   ForEachPanel(k, [&](int first, int kp, int width) {
     PanelReserve(width, kp);
     PanelTimer timer(&w, S(stream_));
@@ -335,9 +336,172 @@ void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts
     o.x = w.cols.get();
     Check(milp_launch::panel_override(width, o, starts[first + kp] - starts[first], S(stream_)),
           "row panel overrides");
-    RowPanelSums(first, kp, width, &timer, out);
+    RowPanelSums(first, kp, width, &timer, sink);
   });
+  return 8 * int64_t(n_total_) + 12 * overrides + 8 * (int64_t(k) + 1);
+}
+
+void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
+  panel_->last_row_panel = LastRowPanel();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("row sums panel");
+  RowPanelSink sink;
+  sink.sums = out;
+  RowPanels(x, k, sink);
+  DeviceOp("row sums panel done");
+}
+
+void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts,
+                                const int32_t* cols, const double* vals, double* out) {
+  panel_->last_row_panel = LastRowPanel();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("row sums panel from");
+  RowPanelSink sink;
+  sink.sums = out;
+  panel_->last_row_panel.overrides_up_bytes = RowPanelsFrom(base, k, starts, cols, vals, sink);
   DeviceOp("row sums panel from done");
+}
+
+static_assert(sizeof(milp_kernels::PointViolations) == sizeof(mi_lp_point_violations) &&
+                  sizeof(mi_lp_point_violations) == 24 &&
+                  offsetof(milp_kernels::PointViolations, worst) ==
+                      offsetof(mi_lp_point_violations, worst) &&
+                  offsetof(milp_kernels::PointViolations, worst_row) ==
+                      offsetof(mi_lp_point_violations, worst_row),
+              "kernel_args.h restates mi_lp_point_violations");
+
+DeviceLp::LastRowViolations DeviceLp::last_row_violations() const {
+  return panel_->last_row_violations;
+}
+
+// The interleaved sums of one panel are in `rows`: count, offsets, fold and
+// write on the device; then down come the kp totals (lists), the kp
+// summaries (summaries) and exactly the kept entries, appended point-major.
+void DeviceLp::RowPanelViolations(int first, int kp, int width, PanelTimer* timer,
+                                  const RowPanelSink& sink) {
+  PanelWorkspace& w = *panel_;
+  RowViolations* out = sink.violations;
+  const int tiles = (m_ + milp_kernels::kPanelTileColumns - 1) / milp_kernels::kPanelTileColumns;
+  w.counts.Reserve(size_t(kp) * tiles, "panel counts");
+  w.tile_worst.Reserve(size_t(kp) * tiles, "panel tile worst");
+  w.tile_worst_row.Reserve(size_t(kp) * tiles, "panel tile worst row");
+  milp_kernels::RowViolationArgs a{};
+  a.in = w.rows.get();
+  a.num_rows = m_;
+  a.kp = kp;
+  a.tiles = tiles;
+  a.row_lb = w.row_lb.get();
+  a.row_ub = w.row_ub.get();
+  a.tolerance = sink.tolerance;
+  a.counts = w.counts.get();
+  a.tile_worst = w.tile_worst.get();
+  a.tile_worst_row = w.tile_worst_row.get();
+  const int64_t* totals = nullptr;
+  if (sink.lists) {
+    // `flat` held the points on their way up; the interleave that read them
+    // is ahead of the write pass on the stream.
+    w.kept_cols.Reserve(size_t(m_) * kp, "panel kept rows");
+    w.offsets.Reserve(size_t(kp) * tiles + milp_kernels::kPanelMaxWidth, "panel offsets");
+    totals = w.totals.Reserve(milp_kernels::kPanelMaxWidth, "panel totals");
+    a.offsets = w.offsets.get();
+    a.totals = w.offsets.get() + size_t(kp) * tiles;
+    a.rows = w.kept_cols.get();
+    a.activities = w.flat.get();
+  }
+  const milp_kernels::PointViolations* host_summaries = nullptr;
+  if (sink.summaries) {
+    a.summaries = w.summaries.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
+    host_summaries = w.summaries_host.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
+  }
+  Check(milp_launch::row_violations_panel(width, a, S(stream_)), "row violations panel");
+  timer->Launched();
+  if (sink.summaries) {
+    Download(w.summaries_host.get(), a.summaries, size_t(kp) * sizeof(*a.summaries));
+    for (int v = 0; v < kp; ++v) {
+      const milp_kernels::PointViolations& s = host_summaries[v];
+      if (s.count < 0 || s.count > m_ || s.worst_row < -1 || s.worst_row >= m_) {
+        throw DeviceError("row violations panel: bad summary");
+      }
+      mi_lp_point_violations& d = out->summaries[first + v];
+      d.count = s.count;
+      d.worst = s.worst;
+      d.worst_row = s.worst_row;
+      d.reserved = 0;
+    }
+    w.last_row_violations.bytes_down += int64_t(kp) * 24;
+  }
+  int64_t kept = 0;
+  if (sink.lists) {
+    Download(w.totals.get(), a.totals, size_t(kp) * sizeof(int64_t));
+    for (int v = 0; v < kp; ++v) {
+      if (totals[v] < 0 || totals[v] > m_) throw DeviceError("row violations panel: bad count");
+      kept += totals[v];
+      out->row_starts[first + v + 1] = out->row_starts[first + v] + totals[v];
+    }
+    const size_t old = out->rows.size();
+    out->rows.resize(old + size_t(kept));
+    out->activities.resize(old + size_t(kept));
+    if (kept > 0) {
+      Check(hipMemcpyAsync(out->rows.data() + old, a.rows, size_t(kept) * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+      Download(out->activities.data() + old, a.activities, size_t(kept) * sizeof(double));
+    }
+    w.last_row_violations.bytes_down += int64_t(kp) * 8 + kept * 12;
+  }
+  timer->Downloaded();
+  w.last_row_violations.panels += 1;
+  w.last_row_violations.width = width;
+  w.last_row_violations.kept += kept;
+}
+
+bool DeviceLp::RowViolationsBegin(int k, const double* row_lb, const double* row_ub, bool lists,
+                                  bool summaries, RowViolations* out) {
+  PanelWorkspace& w = *panel_;
+  w.last_row_violations = LastRowViolations();
+  w.last_row_violations.lists = lists;
+  const size_t points = size_t(std::max(k, 0));
+  out->row_starts.assign(lists ? points + 1 : 0, 0);
+  out->rows.clear();
+  out->activities.clear();
+  out->summaries.assign(summaries ? points : 0, mi_lp_point_violations{0, 0.0, -1, 0});
+  if (k <= 0 || m_ <= 0) return false;
+  Upload(w.row_lb.Reserve(size_t(m_), "panel row lower bounds"), row_lb,
+         size_t(m_) * sizeof(double));
+  Upload(w.row_ub.Reserve(size_t(m_), "panel row upper bounds"), row_ub,
+         size_t(m_) * sizeof(double));
+  return true;
+}
+
+void DeviceLp::RowViolationsPanel(const double* x, int k, const double* row_lb,
+                                  const double* row_ub, double tolerance, bool lists,
+                                  bool summaries, RowViolations* out) {
+  if (!RowViolationsBegin(k, row_lb, row_ub, lists, summaries, out)) return;
+  DeviceOp("row violations panel");
+  RowPanelSink sink;
+  sink.violations = out;
+  sink.tolerance = tolerance;
+  sink.lists = lists;
+  sink.summaries = summaries;
+  RowPanels(x, k, sink);
+  DeviceOp("row violations panel done");
+}
+
+void DeviceLp::RowViolationsPanelFrom(const double* base, int k, const int64_t* starts,
+                                      const int32_t* cols, const double* vals,
+                                      const double* row_lb, const double* row_ub,
+                                      double tolerance, bool lists, bool summaries,
+                                      RowViolations* out) {
+  if (!RowViolationsBegin(k, row_lb, row_ub, lists, summaries, out)) return;
+  DeviceOp("row violations panel from");
+  RowPanelSink sink;
+  sink.violations = out;
+  sink.tolerance = tolerance;
+  sink.lists = lists;
+  sink.summaries = summaries;
+  panel_->last_row_violations.overrides_up_bytes =
+      RowPanelsFrom(base, k, starts, cols, vals, sink);
+  DeviceOp("row violations panel from done");
 }
 
 }  // namespace milp

@@ -2,6 +2,8 @@
 // DeviceLp method, so that a test can run a single device operation on inputs
 // it chooses. A handle owns its CompactSparseMatrix pair and its DeviceLp;
 // there is no RevisedSimplex behind it.
+#include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <exception>
 #include <string>
@@ -391,6 +393,91 @@ int RowPanelGeometry(mi_devop_row_panel_geometry* out) {
   return 0;
 }
 
+// Both violations entries: run(lists, summaries, &result), then the outputs,
+// unless the lists need more than `capacity` entries.
+template <typename Run>
+int RowViolationsCall(mi_devop* h, const char* name, int k, const double* row_lb,
+                      const double* row_ub, double tolerance, int64_t* row_starts, int32_t* rows,
+                      double* activities, int64_t capacity, mi_devop_point_violations* summaries,
+                      Run run) {
+  bool too_large = false;
+  const int rc = Guard(h, [&] {
+    const int m = h->csc.num_rows();
+    bool ok = row_lb != nullptr && row_ub != nullptr && tolerance >= 0.0 &&
+              !std::isinf(tolerance) && (row_starts != nullptr || summaries != nullptr);
+    for (int r = 0; ok && r < m; ++r) {
+      ok = row_lb[r] == row_lb[r] && row_ub[r] == row_ub[r] && row_lb[r] < HUGE_VAL &&
+           row_ub[r] > -HUGE_VAL;
+    }
+    if (!ok) throw milp::DeviceError(std::string(name) + ": bad bounds, tolerance or outputs");
+    milp::DeviceLp::RowViolations result;
+    run(row_starts != nullptr, summaries != nullptr, &result);
+    if (row_starts != nullptr) {
+      const int64_t kept = result.row_starts.back();
+      if (kept > capacity) {
+        too_large = true;
+        throw milp::DeviceError(std::string(name) + ": " + std::to_string(kept) +
+                                " entries, capacity " + std::to_string(capacity));
+      }
+      std::memcpy(row_starts, result.row_starts.data(),
+                  result.row_starts.size() * sizeof(int64_t));
+      if (kept > 0) {
+        std::memcpy(rows, result.rows.data(), size_t(kept) * sizeof(int32_t));
+        std::memcpy(activities, result.activities.data(), size_t(kept) * sizeof(double));
+      }
+    }
+    if (summaries != nullptr && k > 0) {
+      std::memcpy(summaries, result.summaries.data(), size_t(k) * sizeof(*summaries));
+    }
+  });
+  return too_large ? int{MI_DEVOP_CAPACITY} : rc;
+}
+
+int RowViolationsPanel(mi_devop* h, const double* x, int k, const double* row_lb,
+                       const double* row_ub, double tolerance, int64_t* row_starts, int32_t* rows,
+                       double* activities, int64_t capacity,
+                       mi_devop_point_violations* summaries) {
+  return RowViolationsCall(
+      h, "row_violations_panel", k, row_lb, row_ub, tolerance, row_starts, rows, activities,
+      capacity, summaries, [&](bool lists, bool sums, milp::DeviceLp::RowViolations* out) {
+        h->dev.RowViolationsPanel(x, k, row_lb, row_ub, tolerance, lists, sums, out);
+      });
+}
+
+int RowViolationsPanelFrom(mi_devop* h, const double* base, int k, const int64_t* starts,
+                           const int32_t* cols, const double* vals, const double* row_lb,
+                           const double* row_ub, double tolerance, int64_t* row_starts,
+                           int32_t* rows, double* activities, int64_t capacity,
+                           mi_devop_point_violations* summaries) {
+  return RowViolationsCall(
+      h, "row_violations_panel_from", k, row_lb, row_ub, tolerance, row_starts, rows, activities,
+      capacity, summaries, [&](bool lists, bool sums, milp::DeviceLp::RowViolations* out) {
+        if (!milp::DeviceLp::ValidOverrides(h->csc.num_cols(), k, starts, cols) ||
+            (starts[k] > 0 && vals == nullptr)) {
+          throw milp::DeviceError("row_violations_panel_from: bad overrides");
+        }
+        h->dev.RowViolationsPanelFrom(base, k, starts, cols, vals, row_lb, row_ub, tolerance,
+                                      lists, sums, out);
+      });
+}
+
+int LastRowViolations(mi_devop* h, mi_devop_row_violations* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastRowViolations p = h->dev.last_row_violations();
+    out->panels = p.panels;
+    out->width = p.width;
+    out->lists = p.lists ? 1 : 0;
+    out->reserved = 0;
+    out->kept = p.kept;
+    out->bytes_down = p.bytes_down;
+    out->overrides_up_bytes = p.overrides_up_bytes;
+  });
+}
+
+static_assert(sizeof(mi_devop_point_violations) == sizeof(mi_lp_point_violations) &&
+                  offsetof(mi_devop_point_violations, worst_row) ==
+                      offsetof(mi_lp_point_violations, worst_row),
+              "mi_lp_devop.h restates mi_lp_point_violations");
 static_assert(int{MI_DEVOP_ROW_PANEL_DIRECT} == int{milp::DeviceLp::kRowPanelDirect},
               "mi_lp_devop.h restates DeviceLp's row panel paths");
 static_assert(int{MI_DEVOP_PANEL_LONG_COLUMNS} == int{milp::DeviceLp::kPanelLongColumns},
@@ -425,4 +512,6 @@ extern "C" const mi_devop_api mi_devop_table = {
     LastFlips,
     RowSumsPanel,     RowSumsPanelFrom,
     LastRowPanel,     RowPanelGeometry,
+    RowViolationsPanel, RowViolationsPanelFrom,
+    LastRowViolations,
 };

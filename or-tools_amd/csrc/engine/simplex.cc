@@ -5716,6 +5716,10 @@ struct mi_lp {
   std::vector<std::vector<std::pair<int, double>>> dictionary;  // mi_lp_compute_dictionary
   milp::DeviceLp::SparseRows sparse_rows;  // the last mi_lp_*_sparse result
   bool sparse_rows_stored = false;
+  // The lists of the last mi_lp_column_combinations*_violations call that
+  // built them (its summaries are not kept).
+  milp::DeviceLp::RowViolations violated_rows;
+  bool violated_rows_stored = false;
   milp::GlopParameters params;
   milp::LinearProgram lp;
   int device = 0;
@@ -6054,6 +6058,7 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t*
   if (h->running) return MI_LP_ERROR_STATE;
   if (cs[n] > 0 && (ri == nullptr || vals == nullptr)) return MI_LP_ERROR_NULL;
   h->sparse_rows_stored = false;  // mi_lp_get_sparse_rows: rows of the LP before
+  h->violated_rows_stored = false;  // mi_lp_get_violated_rows: likewise
   if ((n > 0 && (clb == nullptr || cub == nullptr || obj == nullptr)) ||
       (m > 0 && (rlb == nullptr || rub == nullptr))) {
     return MI_LP_ERROR_NULL;
@@ -6392,6 +6397,109 @@ int mi_lp_column_combinations_from(mi_lp* h, const double* base, int32_t k,
     h->simplex.device().RowSumsPanelFrom(base, k, starts, cols, vals, out);
     return MI_LP_OK;
   });
+}
+
+}  // extern "C"
+
+namespace {
+// The argument checks the two violations calls share; MI_LP_OK when they
+// pass. A NULL bound array becomes the loaded one.
+int CheckViolationArgs(const mi_lp* h, int32_t k, const double** row_lb, const double** row_ub,
+                       double tolerance) {
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0 || !(tolerance >= 0.0) || std::isinf(tolerance)) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (*row_lb == nullptr) *row_lb = h->lp.row_lb.data();
+  if (*row_ub == nullptr) *row_ub = h->lp.row_ub.data();
+  const double inf = std::numeric_limits<double>::infinity();
+  for (int r = 0; r < h->lp.m; ++r) {
+    const double lb = (*row_lb)[r];
+    const double ub = (*row_ub)[r];
+    if (lb != lb || ub != ub || lb == inf || ub == -inf) return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  return MI_LP_OK;
+}
+
+// run(lists, summaries, &result) computes; then the outputs are written and,
+// when lists were built, the result becomes the stored one. Nothing is
+// written or stored unless run returns MI_LP_OK.
+template <typename Run>
+int ViolationsCall(mi_lp* h, int32_t k, int64_t* row_starts, mi_lp_point_violations* summaries,
+                   Run run) {
+  return PanelCall(h, [&]() -> int {
+    milp::DeviceLp::RowViolations result;
+    const int bad = run(row_starts != nullptr, summaries != nullptr, &result);
+    if (bad != MI_LP_OK) return bad;
+    if (summaries != nullptr) std::copy(result.summaries.begin(), result.summaries.end(), summaries);
+    if (row_starts != nullptr) {
+      std::copy(result.row_starts.begin(), result.row_starts.end(), row_starts);
+      result.summaries.clear();
+      h->violated_rows = std::move(result);
+      h->violated_rows_stored = true;
+    }
+    return MI_LP_OK;
+  });
+}
+}  // namespace
+
+extern "C" {
+
+int mi_lp_column_combinations_violations(mi_lp* h, const double* x, int32_t k,
+                                         const double* row_lb, const double* row_ub,
+                                         double tolerance, int64_t* row_starts,
+                                         mi_lp_point_violations* summaries) {
+  if (h == nullptr || x == nullptr || (row_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckViolationArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  return ViolationsCall(h, k, row_starts, summaries,
+                        [&](bool lists, bool with_summaries, milp::DeviceLp::RowViolations* out) {
+                          h->simplex.device().RowViolationsPanel(x, k, row_lb, row_ub, tolerance,
+                                                                 lists, with_summaries, out);
+                          return int{MI_LP_OK};
+                        });
+}
+
+int mi_lp_column_combinations_from_violations(mi_lp* h, const double* base, int32_t k,
+                                              const int64_t* starts, const int32_t* cols,
+                                              const double* vals, const double* row_lb,
+                                              const double* row_ub, double tolerance,
+                                              int64_t* row_starts,
+                                              mi_lp_point_violations* summaries) {
+  if (h == nullptr || base == nullptr || starts == nullptr ||
+      (row_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckViolationArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  return ViolationsCall(
+      h, k, row_starts, summaries,
+      [&](bool lists, bool with_summaries, milp::DeviceLp::RowViolations* out) -> int {
+        // As mi_lp_column_combinations_from: starts[k] is read only once the
+        // entries before it are known to ascend from 0.
+        if (starts[0] != 0) return MI_LP_ERROR_INVALID_PROBLEM;
+        for (int32_t j = 0; j < k; ++j) {
+          if (starts[j + 1] < starts[j]) return MI_LP_ERROR_INVALID_PROBLEM;
+        }
+        if (starts[k] > 0 && (cols == nullptr || vals == nullptr)) return MI_LP_ERROR_NULL;
+        if (!milp::DeviceLp::ValidOverrides(h->lp.n + h->lp.m, k, starts, cols)) {
+          return MI_LP_ERROR_INVALID_PROBLEM;
+        }
+        h->simplex.device().RowViolationsPanelFrom(base, k, starts, cols, vals, row_lb, row_ub,
+                                                   tolerance, lists, with_summaries, out);
+        return MI_LP_OK;
+      });
+}
+
+int mi_lp_get_violated_rows(const mi_lp* h, int32_t* rows, double* activities) {
+  if (h == nullptr || rows == nullptr || activities == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->violated_rows_stored) return MI_LP_ERROR_STATE;
+  const size_t kept = h->violated_rows.rows.size();
+  if (kept > 0) {
+    std::memcpy(rows, h->violated_rows.rows.data(), kept * sizeof(int32_t));
+    std::memcpy(activities, h->violated_rows.activities.data(), kept * sizeof(double));
+  }
+  return MI_LP_OK;
 }
 
 int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals) {

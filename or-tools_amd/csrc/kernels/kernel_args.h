@@ -124,6 +124,39 @@ struct RowPanelOverrideArgs {
   double* x;
 };
 
+// The violated rows of the row-sum panel result and one summary per point
+// (panel_kernels.hip, violations_count / panel_offsets / violations_fold /
+// violations_write; include/mi_lp.h mi_lp_column_combinations_violations).
+// Row r is violated at point v when a = in[r * K + v] has
+// !(a >= row_lb[r] - tolerance) || !(a <= row_ub[r] + tolerance); both
+// widened bounds are formed in the kernels, one rounded operation each. Its
+// amount is +inf for a NaN a, else max(row_lb[r] - a, a - row_ub[r]).
+// Point v's violated rows, ascending, start at the sum of totals[0 .. v) in
+// rows / activities. The tiles are kPanelTileColumns consecutive rows.
+struct PointViolations {  // mi_lp_point_violations of include/mi_lp.h
+  int64_t count;
+  double worst;
+  int32_t worst_row;
+  int32_t reserved;
+};
+struct RowViolationArgs {
+  const double* in;      // interleaved row sums, num_rows x K
+  int num_rows;
+  int kp;                // points in use (<= K)
+  int tiles;             // ceil(num_rows / kPanelTileColumns)
+  const double* row_lb;  // num_rows
+  const double* row_ub;
+  double tolerance;
+  int* counts;           // kp x tiles
+  double* tile_worst;    // kp x tiles: the largest amount of (point, tile), 0.0 without one
+  int32_t* tile_worst_row;  // kp x tiles: the lowest row attaining it
+  int64_t* offsets;      // kp x tiles
+  int64_t* totals;       // kp
+  PointViolations* summaries;  // kp, or nullptr: no fold
+  int32_t* rows;         // packed output, or nullptr: no offsets and no write pass
+  double* activities;
+};
+
 // Where an update-row kernel that emits the list itself puts it: the
 // ascending listed columns, their coefficients and the count, on the device
 // and (optional, null when off) mirrored into mapped host memory.
@@ -515,6 +548,11 @@ hipError_t panel_fill(int width, const double* base, int ncols, int kp, double* 
 // num_overrides = starts[kp] - starts[0] (known to the host).
 hipError_t panel_override(int width, const milp_kernels::RowPanelOverrideArgs& args,
                           int64_t num_overrides, hipStream_t s);
+// After row_sums_panel on the same stream: violations_count, then (rows !=
+// nullptr) panel_offsets, (summaries != nullptr) violations_fold, and (rows
+// != nullptr) violations_write.
+hipError_t row_violations_panel(int width, const milp_kernels::RowViolationArgs& args,
+                                hipStream_t s);
 hipError_t dense_pack(const int64_t* starts, const double* vals, const int32_t* dense_cols,
                       int nd, int m, double* body, double* tail, hipStream_t s);
 hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hipStream_t s);

@@ -20,7 +20,9 @@
 //
 // The other direction, row sums [A | I] x for a panel of K points
 // (row_sums_panel_kernel and the kernels that build its interleaved points:
-// interleave, panel_fill, panel_override), follows the sparse form.
+// interleave, panel_fill, panel_override), follows the sparse form, and its
+// own sparse form (violations_count / violations_fold / violations_write:
+// the rows outside their bounds and one summary per point) comes last.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -310,46 +312,67 @@ __global__ __launch_bounds__(kPanelOffsetsStep) void panel_offsets_kernel(PanelS
 // bank pair; the row reads are consecutive doubles and conflict-free at any
 // stride. Wave w then takes the vectors w, w + 4, ... < kp: per 64 columns a
 // ballot of the keep rule, rank = the kept lanes below + the kept columns of
-// the chunks before.
+// the chunks before. The rule is the caller's, keep(x, column): the sparse
+// rows and the violated rows (below) share the pass.
 template <int K>
-__global__ __launch_bounds__(kPanelTileColumns) void panel_write_kernel(PanelSparseArgs a) {
-  constexpr int kStride = kPanelTileColumns + (K == 1 ? 0 : 16 / K);
-  __shared__ double tile_vals[K * kStride];
+constexpr int panel_write_stride() {
+  return kPanelTileColumns + (K == 1 ? 0 : 16 / K);
+}
+
+template <int K, typename Keep>
+__device__ __forceinline__ void panel_write_tile(const double* __restrict__ in_all, int ncols,
+                                                 int kp, int tiles,
+                                                 const int64_t* __restrict__ offsets, Keep keep_rule,
+                                                 int32_t* __restrict__ out_cols,
+                                                 double* __restrict__ out_vals,
+                                                 double* tile_vals) {
+  constexpr int kStride = panel_write_stride<K>();
   const int t = threadIdx.x;
   const int tile = blockIdx.x;
   const int col0 = tile * kPanelTileColumns;
-  const int cols = min(kPanelTileColumns, a.ncols - col0);
-  const double* __restrict__ in = a.in + static_cast<int64_t>(col0) * K;
+  const int cols = min(kPanelTileColumns, ncols - col0);
+  const double* __restrict__ in = in_all + static_cast<int64_t>(col0) * K;
   {
     const int v = t % K;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
       const int cl = t / K + j * (kPanelTileColumns / K);
-      if (cl < cols && v < a.kp) tile_vals[v * kStride + cl] = in[t + j * kPanelTileColumns];
+      if (cl < cols && v < kp) tile_vals[v * kStride + cl] = in[t + j * kPanelTileColumns];
     }
   }
   __syncthreads();
   const int lane = t & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(t / kWave);
-  for (int v = wave; v < a.kp; v += kPanelTileColumns / kWave) {
-    int64_t pos = a.offsets[static_cast<int64_t>(v) * a.tiles + tile];
+  for (int v = wave; v < kp; v += kPanelTileColumns / kWave) {
+    int64_t pos = offsets[static_cast<int64_t>(v) * tiles + tile];
     for (int chunk = 0; chunk * kWave < cols; ++chunk) {
       const int cl = chunk * kWave + lane;
       double x = 0.0;
       bool keep = false;
       if (cl < cols) {
         x = tile_vals[v * kStride + cl];
-        keep = panel_keep(x, panel_mask_bit(a.mask, col0 + cl), a.drop_tolerance);
+        keep = keep_rule(x, col0 + cl);
       }
       const unsigned long long kept = __ballot(keep);
       if (keep) {
         const int64_t at = pos + __popcll(kept & ((1ull << lane) - 1ull));
-        a.cols[at] = col0 + cl;
-        a.vals[at] = x;
+        out_cols[at] = col0 + cl;
+        out_vals[at] = x;
       }
       pos += __popcll(kept);
     }
   }
+}
+
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void panel_write_kernel(PanelSparseArgs a) {
+  __shared__ double tile_vals[K * panel_write_stride<K>()];
+  panel_write_tile<K>(
+      a.in, a.ncols, a.kp, a.tiles, a.offsets,
+      [&a](double x, int col) {
+        return panel_keep(x, panel_mask_bit(a.mask, col), a.drop_tolerance);
+      },
+      a.cols, a.vals, tile_vals);
 }
 
 // ---------------------------------------------------------------------------
@@ -451,6 +474,171 @@ __global__ __launch_bounds__(256) void panel_override_kernel(RowPanelOverrideArg
   }
 }
 
+// ---------------------------------------------------------------------------
+// Violated rows and per-point summaries out of row_sums_panel_kernel's
+// interleaved result (include/mi_lp.h mi_lp_column_combinations_violations),
+// in the sparse rows' scheme: a count pass over tiles of kPanelTileColumns
+// rows, panel_offsets_kernel as it is, a fold of the tile partials into the
+// summaries, and the ordered write pass. Kernel boundaries on one stream are
+// the only ordering; no workgroup waits for another.
+
+// The keep rule of the count and the write pass. Both widened bounds are one
+// rounded operation each (-ffp-contract=off); a NaN activity fails both
+// comparisons and is violated.
+__device__ __forceinline__ bool row_violated(double a, double lo, double hi, double tolerance) {
+  return !(a >= lo - tolerance) || !(a <= hi + tolerance);
+}
+
+// The amount of a violated row: > 0 and never NaN (lo != +inf, hi != -inf
+// and a violated +-inf activity has a finite or opposite bound on its side).
+__device__ __forceinline__ double violation_amount(double a, double lo, double hi) {
+  if (a != a) return __builtin_inf();
+  const double below = lo - a;
+  const double above = a - hi;
+  return below > above ? below : above;
+}
+
+// (amount, row) partials: the larger amount, the lower row among equal
+// amounts. Without a violated row a partial is (0.0, kNoWorstRow); every
+// amount is > 0, so any violated row replaces it. Exact and symmetric: the
+// result does not depend on the reduction tree.
+constexpr int kNoWorstRow = 0x7fffffff;
+__device__ __forceinline__ void worst_merge(double* amount, int* row, double other_amount,
+                                            int other_row) {
+  if (other_amount > *amount || (other_amount == *amount && other_row < *row)) {
+    *amount = other_amount;
+    *row = other_row;
+  }
+}
+
+// panel_count_kernel's tile and thread layout: thread t reads elements t,
+// t + 256, ... of the tile's 256 * K contiguous doubles and meets one point
+// only, v = t % K, at rows t / K + j * (256 / K), ascending in j. The lanes
+// of a point combine by shuffles, the four waves through LDS.
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void violations_count_kernel(
+    RowViolationArgs a) {
+  static_assert(kPanelTileColumns == 256 && kPanelTileColumns % K == 0 && kWave % K == 0,
+                "a thread owns one point");
+  constexpr int kWaves = kPanelTileColumns / kWave;
+  __shared__ int wave_count[kWaves][K];
+  __shared__ double wave_amount[kWaves][K];
+  __shared__ int wave_row[kWaves][K];
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int row0 = tile * kPanelTileColumns;
+  const int rows = min(kPanelTileColumns, a.num_rows - row0);
+  const double* __restrict__ in = a.in + static_cast<int64_t>(row0) * K;
+  const int v = t % K;
+  int c = 0;
+  double amount = 0.0;
+  int worst_row = kNoWorstRow;
+  if (v < a.kp) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int rl = t / K + j * (kPanelTileColumns / K);
+      if (rl < rows) {
+        const double x = in[t + j * kPanelTileColumns];
+        const double lo = a.row_lb[row0 + rl];
+        const double hi = a.row_ub[row0 + rl];
+        if (row_violated(x, lo, hi, a.tolerance)) {
+          ++c;
+          worst_merge(&amount, &worst_row, violation_amount(x, lo, hi), row0 + rl);
+        }
+      }
+    }
+  }
+  // Lanes l, l + K, l + 2K, ... of a wave hold the same point.
+#pragma unroll
+  for (int off = K; off < kWave; off <<= 1) {
+    c += __shfl_xor(c, off, kWave);
+    const double other_amount = __shfl_xor(amount, off, kWave);
+    const int other_row = __shfl_xor(worst_row, off, kWave);
+    worst_merge(&amount, &worst_row, other_amount, other_row);
+  }
+  const int lane = t & (kWave - 1);
+  const int wave = t / kWave;
+  if (lane < K) {  // lane == v
+    wave_count[wave][lane] = c;
+    wave_amount[wave][lane] = amount;
+    wave_row[wave][lane] = worst_row;
+  }
+  __syncthreads();
+  if (t < a.kp) {
+    c = wave_count[0][t];
+    amount = wave_amount[0][t];
+    worst_row = wave_row[0][t];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) {
+      c += wave_count[w][t];
+      worst_merge(&amount, &worst_row, wave_amount[w][t], wave_row[w][t]);
+    }
+    const int64_t at = static_cast<int64_t>(t) * a.tiles + tile;
+    a.counts[at] = c;
+    a.tile_worst[at] = amount;
+    a.tile_worst_row[at] = worst_row;
+  }
+}
+
+// Workgroup v folds point v's tile partials into its summary: the integer
+// sum of the counts, the largest amount and the lowest row attaining it.
+__global__ __launch_bounds__(kPanelOffsetsStep) void violations_fold_kernel(RowViolationArgs a) {
+  constexpr int kWaves = kPanelOffsetsStep / kWave;
+  __shared__ long long wave_count[kWaves];
+  __shared__ double wave_amount[kWaves];
+  __shared__ int wave_row[kWaves];
+  const int t = threadIdx.x;
+  const int v = blockIdx.x;  // < kp: the grid is exactly kp workgroups
+  const int64_t base = static_cast<int64_t>(v) * a.tiles;
+  long long c = 0;
+  double amount = 0.0;
+  int worst_row = kNoWorstRow;
+  for (int tile = t; tile < a.tiles; tile += kPanelOffsetsStep) {
+    c += a.counts[base + tile];
+    worst_merge(&amount, &worst_row, a.tile_worst[base + tile], a.tile_worst_row[base + tile]);
+  }
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    c += __shfl_xor(c, off, kWave);
+    const double other_amount = __shfl_xor(amount, off, kWave);
+    const int other_row = __shfl_xor(worst_row, off, kWave);
+    worst_merge(&amount, &worst_row, other_amount, other_row);
+  }
+  if ((t & (kWave - 1)) == 0) {
+    wave_count[t / kWave] = c;
+    wave_amount[t / kWave] = amount;
+    wave_row[t / kWave] = worst_row;
+  }
+  __syncthreads();
+  if (t == 0) {
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) {
+      c += wave_count[w];
+      worst_merge(&amount, &worst_row, wave_amount[w], wave_row[w]);
+    }
+    PointViolations s;
+    s.count = c;
+    s.worst = c > 0 ? amount : 0.0;
+    s.worst_row = c > 0 ? worst_row : -1;
+    s.reserved = 0;
+    a.summaries[v] = s;
+  }
+}
+
+// panel_write_kernel's pass with the violation rule: rows[offset + rank] and
+// activities[offset + rank] in increasing row order.
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void violations_write_kernel(
+    RowViolationArgs a) {
+  __shared__ double tile_vals[K * panel_write_stride<K>()];
+  panel_write_tile<K>(
+      a.in, a.num_rows, a.kp, a.tiles, a.offsets,
+      [&a](double x, int row) {
+        return row_violated(x, a.row_lb[row], a.row_ub[row], a.tolerance);
+      },
+      a.rows, a.activities, tile_vals);
+}
+
 }  // namespace milp_kernels
 
 namespace milp_launch {
@@ -521,6 +709,30 @@ hipError_t row_sums_panel(int width, const RowPanelArgs& args, hipStream_t s) {
     constexpr int K = decltype(w)::value;
     const int blocks = panel_div_up(args.num_rows, kRowPanelThreads / K);
     row_sums_panel_kernel<K><<<blocks, kRowPanelThreads, 0, s>>>(args);
+  });
+}
+
+hipError_t row_violations_panel(int width, const RowViolationArgs& args, hipStream_t s) {
+  if (args.num_rows <= 0 || args.kp <= 0) return hipSuccess;
+  if (args.tiles != panel_div_up(args.num_rows, kPanelTileColumns)) return hipErrorInvalidValue;
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    violations_count_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+    if (args.rows != nullptr) {
+      PanelSparseArgs o{};  // the fields panel_offsets_kernel reads
+      o.kp = args.kp;
+      o.tiles = args.tiles;
+      o.counts = args.counts;
+      o.offsets = args.offsets;
+      o.totals = args.totals;
+      panel_offsets_kernel<<<1, kPanelOffsetsStep, 0, s>>>(o);
+    }
+    if (args.summaries != nullptr) {
+      violations_fold_kernel<<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
+    }
+    if (args.rows != nullptr) {
+      violations_write_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+    }
   });
 }
 

@@ -28,6 +28,10 @@ ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, 
 SIMPLEX_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                               *([ctypes.c_void_p] * 8), ctypes.c_double, ctypes.c_double,
                               ctypes.c_int32, ctypes.c_void_p, *([ctypes.c_void_p] * 4))
+# include/mi_lp.h mi_lp_point_violations: one summary per point.
+POINT_VIOLATIONS = np.dtype([("count", np.int64), ("worst", np.float64),
+                             ("worst_row", np.int32), ("reserved", np.int32)])
+assert POINT_VIOLATIONS.itemsize == 24
 
 
 def build(jobs=8):
@@ -123,6 +127,11 @@ def lib():
     L.mi_lp_get_sparse_rows.argtypes = [vp, vp, vp]
     L.mi_lp_column_combinations.argtypes = [vp, vp, ctypes.c_int32, vp]
     L.mi_lp_column_combinations_from.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp]
+    L.mi_lp_column_combinations_violations.argtypes = [vp, vp, ctypes.c_int32, vp, vp,
+                                                       ctypes.c_double, vp, vp]
+    L.mi_lp_column_combinations_from_violations.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp,
+                                                            vp, vp, ctypes.c_double, vp, vp]
+    L.mi_lp_get_violated_rows.argtypes = [vp, vp, vp]
     L.mi_lp_solver_params_default.argtypes = [ctypes.POINTER(abi.MiLpSolverParams)]
     L.mi_lp_scale.argtypes = [ctypes.POINTER(abi.MiLpSolverParams), ctypes.c_int32,
                               ctypes.c_int32] + [vp] * 14
@@ -602,11 +611,8 @@ class LpHandle:
         self._call("column_combinations", _p(X), k, _p(out))
         return out[:k]
 
-    def column_combinations_from(self, base, overrides):
-        """column_combinations of the points base with X[j][cols] = vals for
-        overrides[j] = (cols, vals), built on the GPU: only base (n or n+m
-        values) and the override lists go up. No column twice within a point.
-        Returns (k, m)."""
+    def _overrides(self, base, overrides):
+        """(base (1, n+m), k, starts, cols, vals) of the override calls."""
         base = self._points(base, "base")
         if base.shape[0] != 1:
             raise ValueError("base must be one point")
@@ -623,10 +629,71 @@ class LpHandle:
             starts[j + 1] = starts[j] + len(c)
         cols = np.ascontiguousarray(np.concatenate(cols))
         vals = np.ascontiguousarray(np.concatenate(vals))
+        return base, k, starts, cols, vals
+
+    def column_combinations_from(self, base, overrides):
+        """column_combinations of the points base with X[j][cols] = vals for
+        overrides[j] = (cols, vals), built on the GPU: only base (n or n+m
+        values) and the override lists go up. No column twice within a point.
+        Returns (k, m)."""
+        base, k, starts, cols, vals = self._overrides(base, overrides)
         out = np.zeros((max(k, 1), self.lp.m), np.float64)
         self._call("column_combinations_from", _p(base), k, _p(starts),
                    _p(cols) if len(cols) else None, _p(vals) if len(vals) else None, _p(out))
         return out[:k]
+
+    def _row_bounds(self, bounds, what):
+        """None (the loaded bounds: NULL in the C call) or m contiguous doubles."""
+        if bounds is None:
+            return None
+        bounds = np.ascontiguousarray(bounds, dtype=np.float64).reshape(-1)
+        if len(bounds) != self.lp.m:
+            raise ValueError(f"{what} must hold {self.lp.m} values, got {len(bounds)}")
+        return bounds
+
+    def _violations(self, name, k, lists, args, row_lb, row_ub, tolerance):
+        """The shared tail of the two violations calls: args are the C call's
+        leading arguments after the handle."""
+        lb, ub = self._row_bounds(row_lb, "row_lb"), self._row_bounds(row_ub, "row_ub")
+        starts = np.zeros(max(k, 1) + 1, np.int64) if lists else None
+        summaries = np.zeros(max(k, 1), POINT_VIOLATIONS)
+        self._call(name, *args, None if lb is None else _p(lb), None if ub is None else _p(ub),
+                   ctypes.c_double(tolerance), None if starts is None else _p(starts),
+                   _p(summaries))
+        if not lists:
+            return None, None, None, summaries[:k]
+        kept = int(starts[k])
+        rows = np.zeros(max(1, kept), np.int32)
+        activities = np.zeros(max(1, kept), np.float64)
+        self._call("get_violated_rows", _p(rows), _p(activities))
+        return starts[:k + 1], rows[:kept], activities[:kept], summaries[:k]
+
+    def column_violations(self, X, row_lb=None, row_ub=None, tolerance=0.0, lists=True):
+        """column_combinations(X) filtered on the GPU: per point the rows whose
+        activity a has not (a >= row_lb - tolerance) or not (a <= row_ub +
+        tolerance), and a summary. X as in column_combinations; row_lb /
+        row_ub: m values, None for the loaded bounds. Returns (row_starts[k+1]
+        int64, rows int32, activities float64, summaries): point j's violated
+        rows, ascending, are rows[row_starts[j]:row_starts[j+1]], and
+        summaries is a structured array (POINT_VIOLATIONS: count, worst,
+        worst_row, reserved) of k entries. With lists=False only the summaries
+        come down and the first three are None."""
+        X = self._points(X, "X")
+        k = X.shape[0]
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            X = np.zeros((1, self.lp.n + self.lp.m), np.float64)
+        return self._violations("column_combinations_violations", k, lists, (_p(X), k),
+                                row_lb, row_ub, tolerance)
+
+    def column_violations_from(self, base, overrides, row_lb=None, row_ub=None, tolerance=0.0,
+                               lists=True):
+        """column_violations of the points of column_combinations_from(base,
+        overrides), built on the GPU."""
+        base, k, starts, cols, vals = self._overrides(base, overrides)
+        return self._violations(
+            "column_combinations_from_violations", k, lists,
+            (_p(base), k, _p(starts), _p(cols) if len(cols) else None,
+             _p(vals) if len(vals) else None), row_lb, row_ub, tolerance)
 
 
 def batch_solve(handles, num_threads=4, progress=None, progress_s=15.0):
