@@ -433,6 +433,97 @@ int mi_lp_column_combinations_from_violations(mi_lp* h, const double* base, int3
                                               mi_lp_point_violations* summaries);
 int mi_lp_get_violated_rows(const mi_lp* h, int32_t* rows, double* activities);
 
+/* Bound sets instead of points: the activity range of every row of A under
+ * each of k bound sets (the children of a node, as mi_lp_batch_solve_bounds
+ * takes them), in one call that reads A once per panel of up to 16 sets: what
+ * a caller reads a child's infeasibility or its residual activities off before
+ * it pays for a solve. Bound sets are over the n structural columns only:
+ * lbs / ubs are k x n, row-major, as for mi_lp_batch_solve_bounds, and the
+ * slack entry that closes every row of [A | I] (column >= n) is no part of a
+ * range. For row r and set j, with l = lbs[j], u = ubs[j]:
+ *   lo = +0.0; hi = +0.0; lo_inf = 0; hi_inf = 0
+ *   for the entries (col, a) of row r with col < n, in increasing column order:
+ *     if a == 0.0: continue                       (+0.0 and -0.0)
+ *     (bl, bh) = (l[col], u[col]) if a > 0.0 else (u[col], l[col])
+ *     if isinf(bl): lo_inf += 1  else: lo = lo + a * bl
+ *     if isinf(bh): hi_inf += 1  else: hi = hi + a * bh
+ * every product and every sum rounded separately (no FMA). An infinite bound
+ * of EITHER sign on the side it is read from is counted and not added: l =
+ * +inf makes the row's minimum unknown (lo_inf > 0), never +inf. A NaN bound
+ * is not infinite and propagates into the sum; a NaN coefficient takes the
+ * else branch; nothing examines l > u. A row without structural entries gives
+ * (+0.0, +0.0, 0, 0).
+ *   mi_lp_bound_activity_ranges       min_activity[j m + r] = lo,
+ *                                     max_activity[j m + r] = hi (k x m each,
+ *                                     vector-major), inf_counts[(j m + r) 2 ..]
+ *                                     = (lo_inf, hi_inf), k x m x 2 int32; it
+ *                                     may be NULL. The caller folds: the
+ *                                     minimum is -inf when lo_inf > 0.
+ *   mi_lp_bound_activity_ranges_from  the same for the sets l_j = base_lb with
+ *                                     l_j[cols[i]] = new_lbs[i], u_j = base_ub
+ *                                     with u_j[cols[i]] = new_ubs[i] for i in
+ *                                     [starts[j], starts[j+1]), built on the
+ *                                     GPU. Bit for bit the dense form on the
+ *                                     materialised sets.
+ * Screening, with lb = row_lb[r], ub = row_ub[r], tol = tolerance:
+ *   g = -inf
+ *   if lo_inf == 0: d = lo - ub;  if d > g: g = d
+ *   if hi_inf == 0: d = lb - hi;  if d > g: g = d
+ *   row r proves set j infeasible iff g > tol
+ * each difference rounded once. A NaN d never replaces g, so g is never NaN:
+ * a NaN bound or a sum that overflowed can only make the screen say "not
+ * proven". The screen is conservative by construction: it never reports a
+ * set that has a point within the bounds and the rows.
+ *   lists      row_starts has k+1 entries; set j's entries are its proving
+ *              rows in strictly increasing order, each with g's bits as its
+ *              amount.
+ *   summaries  mi_lp_point_violations: count the number of proving rows, worst
+ *              the largest g (0.0 when count == 0), worst_row the lowest row
+ *              attaining it (-1 when count == 0). An integer sum, an exact
+ *              maximum and a minimum index: the same bits whatever order the
+ *              GPU reduces in.
+ *   mi_lp_bound_infeasible_rows       compute, store the lists in the handle and
+ *   mi_lp_bound_infeasible_rows_from  write row_starts and summaries;
+ *   mi_lp_get_infeasible_rows         copies the stored rows and amounts out,
+ *                                     row_starts[k] of each.
+ * row_lb / row_ub hold m entries each; either may be NULL and then means the
+ * bounds given to mi_lp_load; +-inf on either side is allowed. summaries may
+ * be NULL. row_starts may be NULL and means summaries only: no list is built,
+ * downloaded or stored, and a previously stored list stays. Both NULL:
+ * MI_LP_ERROR_NULL. The stored list is a third store of the handle, separate
+ * from the sparse rows' and from the violated rows' (none sees or disturbs
+ * another); it lives until the next call that builds these lists, mi_lp_load
+ * or mi_lp_destroy.
+ * Errors, with nothing written and the stored list untouched:
+ * MI_LP_ERROR_INVALID_PROBLEM for k < 0, a tolerance that is negative, NaN or
+ * infinite, a NaN row bound, starts[0] != 0 or starts decreasing, a column
+ * outside [0, n), the same column twice within one set. MI_LP_ERROR_NULL:
+ * NULL h, lbs, ubs, base_lb, base_ub, starts, min_activity or max_activity,
+ * or NULL cols, new_lbs or new_ubs with starts[k] > 0. MI_LP_ERROR_STATE:
+ * before a solve; mi_lp_get_infeasible_rows before any list-building call, or
+ * after mi_lp_load. k = 0 succeeds: the range calls write nothing, the
+ * screening writes row_starts[0] = 0 if row_starts is given and stores an
+ * empty list. No solve uses these calls and they change no state a later
+ * solve reads. */
+int mi_lp_bound_activity_ranges(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                                double* min_activity, double* max_activity,
+                                int32_t* inf_counts);
+int mi_lp_bound_activity_ranges_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                     int32_t k, const int64_t* starts, const int32_t* cols,
+                                     const double* new_lbs, const double* new_ubs,
+                                     double* min_activity, double* max_activity,
+                                     int32_t* inf_counts);
+int mi_lp_bound_infeasible_rows(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                                const double* row_lb, const double* row_ub, double tolerance,
+                                int64_t* row_starts, mi_lp_point_violations* summaries);
+int mi_lp_bound_infeasible_rows_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                     int32_t k, const int64_t* starts, const int32_t* cols,
+                                     const double* new_lbs, const double* new_ubs,
+                                     const double* row_lb, const double* row_ub,
+                                     double tolerance, int64_t* row_starts,
+                                     mi_lp_point_violations* summaries);
+int mi_lp_get_infeasible_rows(const mi_lp* h, int32_t* rows, double* amounts);
+
 /* interrupt may be NULL; a non-zero value stops the solve like a time limit
  * (glop_interface.cc:138-140). */
 int mi_lp_solve(mi_lp* h, const volatile int32_t* interrupt, mi_lp_result* out);

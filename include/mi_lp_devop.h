@@ -229,6 +229,39 @@ typedef struct mi_devop_api {
                                    int32_t* rows, double* activities, int64_t capacity,
                                    mi_devop_point_violations* summaries);
   int (*last_row_violations)(mi_devop* h, mi_devop_row_violations* out);
+  /* Appended after last_row_violations. DeviceLp::BoundRangesPanel (the rule:
+   * include/mi_lp.h mi_lp_bound_activity_ranges). lbs / ubs: k x n over the
+   * structural columns; min_activity / max_activity: k x m; inf_counts:
+   * k x m x 2, or NULL. */
+  int (*bound_ranges_panel)(mi_devop* h, const double* lbs, const double* ubs, int k,
+                            double* min_activity, double* max_activity, int32_t* inf_counts);
+  /* base_lb / base_ub: n; starts: k + 1; cols / new_lbs / new_ubs: starts[k]
+   * entries, NULL when that is 0. Checked here as row_sums_panel_from does,
+   * with the columns in [0, n). */
+  int (*bound_ranges_panel_from)(mi_devop* h, const double* base_lb, const double* base_ub, int k,
+                                 const int64_t* starts, const int32_t* cols,
+                                 const double* new_lbs, const double* new_ubs,
+                                 double* min_activity, double* max_activity,
+                                 int32_t* inf_counts);
+  /* DeviceLp::BoundInfeasiblePanel in one call. row_lb / row_ub: m each, not
+   * NULL, no NaN (+-inf allowed on either side); tolerance finite and >= 0
+   * (checked here). row_starts, rows, amounts, capacity and summaries as
+   * row_violations_panel, MI_DEVOP_CAPACITY included. */
+  int (*bound_infeasible_panel)(mi_devop* h, const double* lbs, const double* ubs, int k,
+                                const double* row_lb, const double* row_ub, double tolerance,
+                                int64_t* row_starts, int32_t* rows, double* amounts,
+                                int64_t capacity, mi_devop_point_violations* summaries);
+  int (*bound_infeasible_panel_from)(mi_devop* h, const double* base_lb, const double* base_ub,
+                                     int k, const int64_t* starts, const int32_t* cols,
+                                     const double* new_lbs, const double* new_ubs,
+                                     const double* row_lb, const double* row_ub,
+                                     double tolerance, int64_t* row_starts, int32_t* rows,
+                                     double* amounts, int64_t capacity,
+                                     mi_devop_point_violations* summaries);
+  /* DeviceLp::LastBoundRanges: the last of the four calls above. bytes_down:
+   * 12 kept + 32 k with lists, 24 k for summaries only; overrides_up_bytes:
+   * 16 n + 20 overrides + 8 (k + 1) for the override forms. */
+  int (*last_bound_ranges)(mi_devop* h, mi_devop_row_violations* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

@@ -290,6 +290,48 @@ class DeviceLp : public DeviceSolver {
   };
   LastRowViolations last_row_violations() const;
 
+  // --- activity ranges of k bound sets in one pass (include/mi_lp.h
+  // mi_lp_bound_activity_ranges has the rule) -----
+  // lbs / ubs are k x n over the structural columns, vector-major on the
+  // host; the slack entry of a row is no part of its range. They travel as
+  // the points of RowSumsPanel do, once per array (up vector-major,
+  // interleaved on the device into the workspace's two column-interleaved
+  // buffers), and activity_ranges_panel_kernel reads the CSR of [A | I] once
+  // per panel. min_activity / max_activity: k x m, vector-major; inf_counts:
+  // k x m x 2 (lo_inf, hi_inf) or null. Writes nothing a solve reads; with
+  // column shards it stays on the unsplit handle, as RowSums does; kernel
+  // time is in TakePanelKernelMs. Synchronizes before it returns.
+  void BoundRangesPanel(const double* lbs, const double* ubs, int k, double* min_activity,
+                        double* max_activity, int32_t* inf_counts);
+  // The same for the bound sets base + overrides: l_j = base_lb with
+  // l_j[cols[i]] = new_lbs[i], u_j likewise, for i in [starts[j],
+  // starts[j + 1]). 16 n + 20 overrides + 8 (k + 1) bytes go up once per
+  // call. Preconditions: ValidOverrides with num_cols = n.
+  void BoundRangesPanelFrom(const double* base_lb, const double* base_ub, int k,
+                            const int64_t* starts, const int32_t* cols, const double* new_lbs,
+                            const double* new_ubs, double* min_activity, double* max_activity,
+                            int32_t* inf_counts);
+  // The screening: the kernel forms g per (row, child) from the two ranges
+  // and the row bounds and stores only g; the count, offsets, fold and write
+  // passes of the row violations then keep the rows with g > tolerance, with
+  // g as the amount (RowViolations::activities holds the amounts). The
+  // summaries are always built: per panel the kp summaries, and with lists
+  // the kp totals and the kept (4-byte row, 8-byte amount) entries come down.
+  void BoundInfeasiblePanel(const double* lbs, const double* ubs, int k, const double* row_lb,
+                            const double* row_ub, double tolerance, bool lists,
+                            RowViolations* out);
+  void BoundInfeasiblePanelFrom(const double* base_lb, const double* base_ub, int k,
+                                const int64_t* starts, const int32_t* cols,
+                                const double* new_lbs, const double* new_ubs,
+                                const double* row_lb, const double* row_ub, double tolerance,
+                                bool lists, RowViolations* out);
+  // The last of these four calls (test record): LastRowViolations' fields.
+  // bytes_down is 12 kept + 32 k with lists, 24 k for summaries only, and
+  // 16 k m (24 k m with counts) for the dense ranges; overrides_up_bytes is
+  // 16 n + 20 overrides + 8 (k + 1) for the override forms.
+  using LastBoundRanges = LastRowViolations;
+  LastBoundRanges last_bound_ranges() const;
+
   // --- dual device mode: device-resident reduced costs ------------------
   // (see simplex.cc RevisedSimplex::DualDeviceMode). colbits: one byte per
   // column (kernel_args.h kCol*), bound_diff: upper - lower per column.
@@ -535,30 +577,41 @@ class DeviceLp : public DeviceSolver {
     int sparse_cols = 0;
   };
   PanelPlan PanelKernelChoice() const;
-  void PanelReserve(int width, int kp);
+  void PanelReserve(int width, int kp, bool ranges = false);
   void PanelUploadVectors(const double* y, int first, int kp, int width);
   void PanelLaunchDots(const PanelPlan& plan, int kp, int width);
   void PanelRecord(const PanelPlan& plan, int width, LastPanel* record) const;
   // What a row-sum call does with each panel's interleaved sums: the dense
-  // form brings them down, the violations form filters them first.
+  // form brings them down, the violations form filters them first. With
+  // `ranges` the points are bound sets over the n structural columns, a
+  // lower and an upper array, and the panel's kernel is the activity ranges
+  // instead of the row sums; everything around the launch is the same path.
   struct RowPanelSink {
     double* sums = nullptr;               // RowSumsPanel(From): k x m on the host
-    RowViolations* violations = nullptr;  // RowViolationsPanel(From)
+    RowViolations* violations = nullptr;  // RowViolationsPanel(From), BoundInfeasiblePanel(From)
     double tolerance = 0.0;
     bool lists = false;
     bool summaries = false;
+    LastRowViolations* record = nullptr;  // the record the filtered form fills
+    bool ranges = false;
+    double* max_activity = nullptr;  // dense ranges: k x m (sums takes the minima)
+    int32_t* inf_counts = nullptr;   // dense ranges: k x m x 2, or null
   };
-  void RowPanels(const double* x, int k, const RowPanelSink& sink);
-  // Returns the bytes that went up once for the call.
-  int64_t RowPanelsFrom(const double* base, int k, const int64_t* starts, const int32_t* cols,
-                        const double* vals, const RowPanelSink& sink);
+  // upper: the second array of a ranges call (k x n beside x's k x n), else
+  // null (x is k x N).
+  void RowPanels(const double* x, const double* upper, int k, const RowPanelSink& sink);
+  // Returns the bytes that went up once for the call. base_upper /
+  // vals_upper: the second array of a ranges call, else null.
+  int64_t RowPanelsFrom(const double* base, const double* base_upper, int k,
+                        const int64_t* starts, const int32_t* cols, const double* vals,
+                        const double* vals_upper, const RowPanelSink& sink);
   void RowPanelSums(int first, int kp, int width, PanelTimer* timer, const RowPanelSink& sink);
   void RowPanelViolations(int first, int kp, int width, PanelTimer* timer,
                           const RowPanelSink& sink);
-  // Resets the record and `out`, uploads the bounds; false when there is
+  // Resets `record` and `out`, uploads the bounds; false when there is
   // nothing to launch (k <= 0 or no rows).
-  bool RowViolationsBegin(int k, const double* row_lb, const double* row_ub, bool lists,
-                          bool summaries, RowViolations* out);
+  bool RowViolationsBegin(LastRowViolations* record, int k, const double* row_lb,
+                          const double* row_ub, bool lists, bool summaries, RowViolations* out);
   bool is_shard_ = false;
   std::vector<std::unique_ptr<DeviceLp>> shards_;  // null: a block owned by another process
   ExchangeFn exchange_fn_ = nullptr;

@@ -1,6 +1,7 @@
 // The workspace of DeviceLp's panel calls (device_panel.hip): the buffers of
-// ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel, RowSumsPanelFrom and
-// RowViolationsPanel(From), their timing events and their test records.
+// ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel, RowSumsPanelFrom,
+// RowViolationsPanel(From), BoundRangesPanel(From) and
+// BoundInfeasiblePanel(From), their timing events and their test records.
 // Included by the HIP translation units only; device_lp.h holds the workspace
 // behind a pointer.
 #ifndef MILP_DEVICE_PANEL_H_
@@ -84,7 +85,19 @@ struct PanelWorkspace {
   // The row violations (RowViolationsPanel, RowViolationsPanelFrom) are row
   // sums up to the results in `rows`; then `flat` takes the packed kept
   // activities (at most kp m <= kp N), the points having left it.
+  //
+  // The bound sets' activity ranges (BoundRangesPanel(From),
+  // BoundInfeasiblePanel(From)) are the row sums' direction with two point
+  // arrays over the n structural columns: `cols` takes the interleaved lower
+  // bounds and `cols_upper` (below) the upper bounds; `flat` takes both
+  // arrays on their way up (2 kp n), `rows` the three result blocks lo, hi
+  // and packed counts (3 m width) or, when screening, g alone (m width), and
+  // `flat` then the results on their way down (3 kp m) or the packed kept
+  // amounts. PanelReserve(ranges) sizes them for that.
   DeviceBuffer<double> rows, cols, flat;
+  // Activity ranges only: the column-interleaved upper bounds, max(1, n)
+  // width, read beside `cols` (the lower bounds) by the kernel.
+  DeviceBuffer<double> cols_upper;
   PinnedBuffer<double> y_staging;  // column dots: the host interleave of y, max(1, m width)
 
   // ColumnDotsPanelSparse and the row violations: tiles of 256 columns
@@ -107,6 +120,10 @@ struct PanelWorkspace {
   DeviceBuffer<int64_t> ov_starts;  // k + 1
   DeviceBuffer<int32_t> ov_cols;    // overrides of the whole call
   DeviceBuffer<double> ov_vals;
+  // BoundRangesPanelFrom and BoundInfeasiblePanelFrom: the upper bounds'
+  // base (n) and override values beside the lower bounds' in base / ov_vals.
+  DeviceBuffer<double> base_upper;
+  DeviceBuffer<double> ov_vals_upper;
 
   // Kernel time (TakePanelKernelMs): off until the first take.
   bool timing = false;
@@ -117,6 +134,7 @@ struct PanelWorkspace {
   DeviceLp::LastPanelSparse last_panel_sparse;
   DeviceLp::LastRowPanel last_row_panel;
   DeviceLp::LastRowViolations last_row_violations;
+  DeviceLp::LastBoundRanges last_bound_ranges;
 };
 
 }  // namespace milp

@@ -1,9 +1,10 @@
 // DeviceLp's panel calls: k vectors per pass over [A | I] (see device_lp.h).
 // Column dots (ColumnDotsPanel, ColumnDotsPanelSparse), row sums (RowSumsPanel,
-// RowSumsPanelFrom) and their violated rows (RowViolationsPanel,
-// RowViolationsPanelFrom) share one workspace (device_panel.h), one panel
-// loop and one timing scope. No solve calls them and nothing a solve
-// reads is written.
+// RowSumsPanelFrom), their violated rows (RowViolationsPanel,
+// RowViolationsPanelFrom) and the activity ranges of bound sets
+// (BoundRangesPanel(From), BoundInfeasiblePanel(From)) share one workspace
+// (device_panel.h), one panel loop and one timing scope. No solve calls them
+// and nothing a solve reads is written.
 #include "device_panel.h"
 
 #include <algorithm>
@@ -91,10 +92,20 @@ void DeviceLp::RowPanelGeometry(int rows_per_workgroup[3], int* chunk) {
 // Grows the three shared buffers to one panel of `width` holding `kp`
 // vectors. The stream is idle between panels (each ends with a synchronizing
 // download).
-void DeviceLp::PanelReserve(int width, int kp) {
-  panel_->rows.Reserve(std::max<size_t>(1, size_t(m_) * width), "panel rows");
+// ranges: the roles of the activity ranges (device_panel.h).
+void DeviceLp::PanelReserve(int width, int kp, bool ranges) {
+  const size_t n = size_t(n_total_ - m_);
+  size_t rows = size_t(m_) * width;
+  size_t flat = size_t(n_total_) * kp;
+  if (ranges) {
+    rows *= 3;
+    flat = std::max(flat, std::max(2 * n, 3 * size_t(m_)) * kp);
+    // At least one column: the kernel redirects a slack's gather to column 0.
+    panel_->cols_upper.Reserve(std::max<size_t>(1, n) * width, "panel upper bounds");
+  }
+  panel_->rows.Reserve(std::max<size_t>(1, rows), "panel rows");
   panel_->cols.Reserve(size_t(n_total_) * width, "panel columns");
-  panel_->flat.Reserve(size_t(n_total_) * kp, "panel vector-major");
+  panel_->flat.Reserve(flat, "panel vector-major");
 }
 
 DeviceLp::PanelPlan DeviceLp::PanelKernelChoice() const {
@@ -272,22 +283,64 @@ bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const 
 void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer,
                             const RowPanelSink& sink) {
   PanelWorkspace& w = *panel_;
-  milp_kernels::RowPanelArgs a{};
-  a.t_starts = d_t_starts_;
-  a.t_cols = d_t_cols_;
-  a.t_vals = d_t_vals_;
-  a.x = w.cols.get();
-  a.num_rows = m_;
-  a.kp = kp;
-  a.out = w.rows.get();
-  Check(milp_launch::row_sums_panel(width, a, S(stream_)), "row sums panel");
+  if (sink.ranges) {
+    milp_kernels::ActivityRangeArgs a{};
+    a.t_starts = d_t_starts_;
+    a.t_cols = d_t_cols_;
+    a.t_vals = d_t_vals_;
+    a.lower = w.cols.get();
+    a.upper = w.cols_upper.get();
+    a.num_rows = m_;
+    a.num_structural = n_total_ - m_;
+    a.kp = kp;
+    if (sink.violations != nullptr) {  // screening: g alone
+      a.row_lb = w.row_lb.get();
+      a.row_ub = w.row_ub.get();
+    }
+    a.out = w.rows.get();
+    Check(milp_launch::activity_ranges_panel(width, a, S(stream_)), "activity ranges panel");
+  } else {
+    milp_kernels::RowPanelArgs a{};
+    a.t_starts = d_t_starts_;
+    a.t_cols = d_t_cols_;
+    a.t_vals = d_t_vals_;
+    a.x = w.cols.get();
+    a.num_rows = m_;
+    a.kp = kp;
+    a.out = w.rows.get();
+    Check(milp_launch::row_sums_panel(width, a, S(stream_)), "row sums panel");
+  }
   if (sink.violations != nullptr) return RowPanelViolations(first, kp, width, timer, sink);
-  Check(milp_launch::panel_deinterleave(width, w.rows.get(), m_, kp, w.flat.get(), m_,
-                                        S(stream_)),
-        "row panel de-interleave");
+  // The dense form: the result blocks of `rows` (one of sums; lo, hi and the
+  // packed counts of ranges), each m x width, go vector-major into `flat`.
+  const size_t block = size_t(m_) * width;
+  const size_t down = size_t(kp) * m_;
+  const int blocks = !sink.ranges ? 1 : (sink.inf_counts != nullptr ? 3 : 2);
+  for (int b = 0; b < blocks; ++b) {
+    Check(milp_launch::panel_deinterleave(width, w.rows.get() + b * block, m_, kp,
+                                          w.flat.get() + b * down, m_, S(stream_)),
+          "row panel de-interleave");
+  }
   timer->Launched();
-  Download(sink.sums + size_t(first) * m_, w.flat.get(), size_t(kp) * m_ * sizeof(double));
+  if (sink.ranges) {
+    Check(hipMemcpyAsync(sink.max_activity + size_t(first) * m_, w.flat.get() + down,
+                         down * sizeof(double), hipMemcpyDeviceToHost, S(stream_)),
+          "D2H");
+    if (sink.inf_counts != nullptr) {
+      // A packed pair lo_inf | hi_inf << 32 is the two int32 of the caller.
+      Check(hipMemcpyAsync(sink.inf_counts + size_t(first) * m_ * 2, w.flat.get() + 2 * down,
+                           down * sizeof(double), hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+    }
+  }
+  Download(sink.sums + size_t(first) * m_, w.flat.get(), down * sizeof(double));
   timer->Downloaded();
+  if (sink.ranges) {
+    w.last_bound_ranges.panels += 1;
+    w.last_bound_ranges.width = width;
+    w.last_bound_ranges.bytes_down += int64_t(blocks) * int64_t(down) * 8;
+    return;
+  }
   w.last_row_panel.panels += 1;
   w.last_row_panel.width = width;
   w.last_row_panel.kernel = kRowPanelDirect;
@@ -295,50 +348,76 @@ void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer,
 
 // The k dense points, panel by panel: up vector-major, interleaved on the
 // device, then RowPanelSums.
-void DeviceLp::RowPanels(const double* x, int k, const RowPanelSink& sink) {
+// A ranges call brings two arrays over the n structural columns: both go up
+// into `flat`, one behind the other, and each is interleaved into its buffer.
+void DeviceLp::RowPanels(const double* x, const double* upper, int k, const RowPanelSink& sink) {
   PanelWorkspace& w = *panel_;
+  const int ncols = sink.ranges ? n_total_ - m_ : n_total_;
   ForEachPanel(k, [&](int first, int kp, int width) {
-    PanelReserve(width, kp);
-    Upload(w.flat.get(), x + size_t(first) * n_total_, size_t(kp) * n_total_ * sizeof(double));
+    PanelReserve(width, kp, sink.ranges);
+    const size_t up = size_t(kp) * ncols;
+    Upload(w.flat.get(), x + size_t(first) * ncols, up * sizeof(double));
+    if (sink.ranges) Upload(w.flat.get() + up, upper + size_t(first) * ncols, up * sizeof(double));
     PanelTimer timer(&w, S(stream_));
-    Check(milp_launch::panel_interleave(width, w.flat.get(), n_total_, n_total_, kp,
-                                        w.cols.get(), S(stream_)),
+    Check(milp_launch::panel_interleave(width, w.flat.get(), ncols, ncols, kp, w.cols.get(),
+                                        S(stream_)),
           "row panel interleave");
+    if (sink.ranges) {
+      Check(milp_launch::panel_interleave(width, w.flat.get() + up, ncols, ncols, kp,
+                                          w.cols_upper.get(), S(stream_)),
+            "row panel interleave");
+    }
     RowPanelSums(first, kp, width, &timer, sink);
   });
 }
 
 // The k points base + overrides: base and the lists go up once, every panel
 // is filled and overridden on the device, then RowPanelSums.
-int64_t DeviceLp::RowPanelsFrom(const double* base, int k, const int64_t* starts,
-                                const int32_t* cols, const double* vals,
-                                const RowPanelSink& sink) {
+int64_t DeviceLp::RowPanelsFrom(const double* base, const double* base_upper, int k,
+                                const int64_t* starts, const int32_t* cols, const double* vals,
+                                const double* vals_upper, const RowPanelSink& sink) {
   PanelWorkspace& w = *panel_;
+  const int ncols = sink.ranges ? n_total_ - m_ : n_total_;
   const int64_t overrides = starts[k];
-  Upload(w.base.Reserve(size_t(n_total_), "panel base point"), base,
-         size_t(n_total_) * sizeof(double));
+  Upload(w.base.Reserve(size_t(ncols), "panel base point"), base, size_t(ncols) * sizeof(double));
   Upload(w.ov_starts.Reserve(size_t(k) + 1, "panel override starts"), starts,
          (size_t(k) + 1) * sizeof(int64_t));
   Upload(w.ov_cols.Reserve(size_t(overrides), "panel override columns"), cols,
          size_t(overrides) * sizeof(int32_t));
   Upload(w.ov_vals.Reserve(size_t(overrides), "panel override values"), vals,
          size_t(overrides) * sizeof(double));
-  ForEachPanel(k, [&](int first, int kp, int width) {
-    PanelReserve(width, kp);
-    PanelTimer timer(&w, S(stream_));
-    Check(milp_launch::panel_fill(width, w.base.get(), n_total_, kp, w.cols.get(), S(stream_)),
+  if (sink.ranges) {
+    Upload(w.base_upper.Reserve(size_t(ncols), "panel base upper bounds"), base_upper,
+           size_t(ncols) * sizeof(double));
+    Upload(w.ov_vals_upper.Reserve(size_t(overrides), "panel override upper bounds"), vals_upper,
+           size_t(overrides) * sizeof(double));
+  }
+  // One interleaved array of the panel: the base in every point, then the
+  // panel's overrides.
+  auto build = [&](const double* device_base, const double* device_vals, double* points,
+                   int first, int kp, int width) {
+    Check(milp_launch::panel_fill(width, device_base, ncols, kp, points, S(stream_)),
           "row panel fill");
     milp_kernels::RowPanelOverrideArgs o{};
     o.starts = w.ov_starts.get() + first;
     o.cols = w.ov_cols.get();
-    o.vals = w.ov_vals.get();
+    o.vals = device_vals;
     o.kp = kp;
-    o.x = w.cols.get();
+    o.x = points;
     Check(milp_launch::panel_override(width, o, starts[first + kp] - starts[first], S(stream_)),
           "row panel overrides");
+  };
+  ForEachPanel(k, [&](int first, int kp, int width) {
+    PanelReserve(width, kp, sink.ranges);
+    PanelTimer timer(&w, S(stream_));
+    build(w.base.get(), w.ov_vals.get(), w.cols.get(), first, kp, width);
+    if (sink.ranges) {
+      build(w.base_upper.get(), w.ov_vals_upper.get(), w.cols_upper.get(), first, kp, width);
+    }
     RowPanelSums(first, kp, width, &timer, sink);
   });
-  return 8 * int64_t(n_total_) + 12 * overrides + 8 * (int64_t(k) + 1);
+  const int arrays = sink.ranges ? 2 : 1;
+  return 8 * int64_t(ncols) * arrays + (4 + 8 * arrays) * overrides + 8 * (int64_t(k) + 1);
 }
 
 void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
@@ -347,7 +426,7 @@ void DeviceLp::RowSumsPanel(const double* x, int k, double* out) {
   DeviceOp("row sums panel");
   RowPanelSink sink;
   sink.sums = out;
-  RowPanels(x, k, sink);
+  RowPanels(x, nullptr, k, sink);
   DeviceOp("row sums panel done");
 }
 
@@ -358,7 +437,8 @@ void DeviceLp::RowSumsPanelFrom(const double* base, int k, const int64_t* starts
   DeviceOp("row sums panel from");
   RowPanelSink sink;
   sink.sums = out;
-  panel_->last_row_panel.overrides_up_bytes = RowPanelsFrom(base, k, starts, cols, vals, sink);
+  panel_->last_row_panel.overrides_up_bytes =
+      RowPanelsFrom(base, nullptr, k, starts, cols, vals, nullptr, sink);
   DeviceOp("row sums panel from done");
 }
 
@@ -413,7 +493,9 @@ void DeviceLp::RowPanelViolations(int first, int kp, int width, PanelTimer* time
     a.summaries = w.summaries.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
     host_summaries = w.summaries_host.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
   }
-  Check(milp_launch::row_violations_panel(width, a, S(stream_)), "row violations panel");
+  const int rule =
+      sink.ranges ? milp_kernels::kRowRuleAboveTolerance : milp_kernels::kRowRuleOutsideBounds;
+  Check(milp_launch::row_violations_panel(width, rule, a, S(stream_)), "row violations panel");
   timer->Launched();
   if (sink.summaries) {
     Download(w.summaries_host.get(), a.summaries, size_t(kp) * sizeof(*a.summaries));
@@ -428,7 +510,7 @@ void DeviceLp::RowPanelViolations(int first, int kp, int width, PanelTimer* time
       d.worst_row = s.worst_row;
       d.reserved = 0;
     }
-    w.last_row_violations.bytes_down += int64_t(kp) * 24;
+    sink.record->bytes_down += int64_t(kp) * 24;
   }
   int64_t kept = 0;
   if (sink.lists) {
@@ -447,19 +529,20 @@ void DeviceLp::RowPanelViolations(int first, int kp, int width, PanelTimer* time
             "D2H");
       Download(out->activities.data() + old, a.activities, size_t(kept) * sizeof(double));
     }
-    w.last_row_violations.bytes_down += int64_t(kp) * 8 + kept * 12;
+    sink.record->bytes_down += int64_t(kp) * 8 + kept * 12;
   }
   timer->Downloaded();
-  w.last_row_violations.panels += 1;
-  w.last_row_violations.width = width;
-  w.last_row_violations.kept += kept;
+  sink.record->panels += 1;
+  sink.record->width = width;
+  sink.record->kept += kept;
 }
 
-bool DeviceLp::RowViolationsBegin(int k, const double* row_lb, const double* row_ub, bool lists,
-                                  bool summaries, RowViolations* out) {
+bool DeviceLp::RowViolationsBegin(LastRowViolations* record, int k, const double* row_lb,
+                                  const double* row_ub, bool lists, bool summaries,
+                                  RowViolations* out) {
   PanelWorkspace& w = *panel_;
-  w.last_row_violations = LastRowViolations();
-  w.last_row_violations.lists = lists;
+  *record = LastRowViolations();
+  record->lists = lists;
   const size_t points = size_t(std::max(k, 0));
   out->row_starts.assign(lists ? points + 1 : 0, 0);
   out->rows.clear();
@@ -476,14 +559,18 @@ bool DeviceLp::RowViolationsBegin(int k, const double* row_lb, const double* row
 void DeviceLp::RowViolationsPanel(const double* x, int k, const double* row_lb,
                                   const double* row_ub, double tolerance, bool lists,
                                   bool summaries, RowViolations* out) {
-  if (!RowViolationsBegin(k, row_lb, row_ub, lists, summaries, out)) return;
+  if (!RowViolationsBegin(&panel_->last_row_violations, k, row_lb, row_ub, lists, summaries,
+                          out)) {
+    return;
+  }
   DeviceOp("row violations panel");
   RowPanelSink sink;
   sink.violations = out;
   sink.tolerance = tolerance;
   sink.lists = lists;
   sink.summaries = summaries;
-  RowPanels(x, k, sink);
+  sink.record = &panel_->last_row_violations;
+  RowPanels(x, nullptr, k, sink);
   DeviceOp("row violations panel done");
 }
 
@@ -492,16 +579,96 @@ void DeviceLp::RowViolationsPanelFrom(const double* base, int k, const int64_t* 
                                       const double* row_lb, const double* row_ub,
                                       double tolerance, bool lists, bool summaries,
                                       RowViolations* out) {
-  if (!RowViolationsBegin(k, row_lb, row_ub, lists, summaries, out)) return;
+  if (!RowViolationsBegin(&panel_->last_row_violations, k, row_lb, row_ub, lists, summaries,
+                          out)) {
+    return;
+  }
   DeviceOp("row violations panel from");
   RowPanelSink sink;
   sink.violations = out;
   sink.tolerance = tolerance;
   sink.lists = lists;
   sink.summaries = summaries;
+  sink.record = &panel_->last_row_violations;
   panel_->last_row_violations.overrides_up_bytes =
-      RowPanelsFrom(base, k, starts, cols, vals, sink);
+      RowPanelsFrom(base, nullptr, k, starts, cols, vals, nullptr, sink);
   DeviceOp("row violations panel from done");
+}
+
+DeviceLp::LastBoundRanges DeviceLp::last_bound_ranges() const {
+  return panel_->last_bound_ranges;
+}
+
+void DeviceLp::BoundRangesPanel(const double* lbs, const double* ubs, int k,
+                                double* min_activity, double* max_activity,
+                                int32_t* inf_counts) {
+  panel_->last_bound_ranges = LastBoundRanges();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("bound ranges panel");
+  RowPanelSink sink;
+  sink.ranges = true;
+  sink.sums = min_activity;
+  sink.max_activity = max_activity;
+  sink.inf_counts = inf_counts;
+  RowPanels(lbs, ubs, k, sink);
+  DeviceOp("bound ranges panel done");
+}
+
+void DeviceLp::BoundRangesPanelFrom(const double* base_lb, const double* base_ub, int k,
+                                    const int64_t* starts, const int32_t* cols,
+                                    const double* new_lbs, const double* new_ubs,
+                                    double* min_activity, double* max_activity,
+                                    int32_t* inf_counts) {
+  panel_->last_bound_ranges = LastBoundRanges();
+  if (k <= 0 || m_ <= 0) return;
+  DeviceOp("bound ranges panel from");
+  RowPanelSink sink;
+  sink.ranges = true;
+  sink.sums = min_activity;
+  sink.max_activity = max_activity;
+  sink.inf_counts = inf_counts;
+  panel_->last_bound_ranges.overrides_up_bytes =
+      RowPanelsFrom(base_lb, base_ub, k, starts, cols, new_lbs, new_ubs, sink);
+  DeviceOp("bound ranges panel from done");
+}
+
+void DeviceLp::BoundInfeasiblePanel(const double* lbs, const double* ubs, int k,
+                                    const double* row_lb, const double* row_ub,
+                                    double tolerance, bool lists, RowViolations* out) {
+  if (!RowViolationsBegin(&panel_->last_bound_ranges, k, row_lb, row_ub, lists, true, out)) {
+    return;
+  }
+  DeviceOp("bound infeasible panel");
+  RowPanelSink sink;
+  sink.ranges = true;
+  sink.violations = out;
+  sink.tolerance = tolerance;
+  sink.lists = lists;
+  sink.summaries = true;
+  sink.record = &panel_->last_bound_ranges;
+  RowPanels(lbs, ubs, k, sink);
+  DeviceOp("bound infeasible panel done");
+}
+
+void DeviceLp::BoundInfeasiblePanelFrom(const double* base_lb, const double* base_ub, int k,
+                                        const int64_t* starts, const int32_t* cols,
+                                        const double* new_lbs, const double* new_ubs,
+                                        const double* row_lb, const double* row_ub,
+                                        double tolerance, bool lists, RowViolations* out) {
+  if (!RowViolationsBegin(&panel_->last_bound_ranges, k, row_lb, row_ub, lists, true, out)) {
+    return;
+  }
+  DeviceOp("bound infeasible panel from");
+  RowPanelSink sink;
+  sink.ranges = true;
+  sink.violations = out;
+  sink.tolerance = tolerance;
+  sink.lists = lists;
+  sink.summaries = true;
+  sink.record = &panel_->last_bound_ranges;
+  panel_->last_bound_ranges.overrides_up_bytes =
+      RowPanelsFrom(base_lb, base_ub, k, starts, cols, new_lbs, new_ubs, sink);
+  DeviceOp("bound infeasible panel from done");
 }
 
 }  // namespace milp

@@ -393,10 +393,11 @@ int RowPanelGeometry(mi_devop_row_panel_geometry* out) {
   return 0;
 }
 
-// Both violations entries: run(lists, summaries, &result), then the outputs,
-// unless the lists need more than `capacity` entries.
+// The violations and the screening entries: run(lists, summaries, &result),
+// then the outputs, unless the lists need more than `capacity` entries.
+// any_bounds: +-inf is allowed on either side (the screening).
 template <typename Run>
-int RowViolationsCall(mi_devop* h, const char* name, int k, const double* row_lb,
+int RowViolationsCall(mi_devop* h, const char* name, bool any_bounds, int k, const double* row_lb,
                       const double* row_ub, double tolerance, int64_t* row_starts, int32_t* rows,
                       double* activities, int64_t capacity, mi_devop_point_violations* summaries,
                       Run run) {
@@ -406,8 +407,8 @@ int RowViolationsCall(mi_devop* h, const char* name, int k, const double* row_lb
     bool ok = row_lb != nullptr && row_ub != nullptr && tolerance >= 0.0 &&
               !std::isinf(tolerance) && (row_starts != nullptr || summaries != nullptr);
     for (int r = 0; ok && r < m; ++r) {
-      ok = row_lb[r] == row_lb[r] && row_ub[r] == row_ub[r] && row_lb[r] < HUGE_VAL &&
-           row_ub[r] > -HUGE_VAL;
+      ok = row_lb[r] == row_lb[r] && row_ub[r] == row_ub[r] &&
+           (any_bounds || (row_lb[r] < HUGE_VAL && row_ub[r] > -HUGE_VAL));
     }
     if (!ok) throw milp::DeviceError(std::string(name) + ": bad bounds, tolerance or outputs");
     milp::DeviceLp::RowViolations result;
@@ -438,7 +439,7 @@ int RowViolationsPanel(mi_devop* h, const double* x, int k, const double* row_lb
                        double* activities, int64_t capacity,
                        mi_devop_point_violations* summaries) {
   return RowViolationsCall(
-      h, "row_violations_panel", k, row_lb, row_ub, tolerance, row_starts, rows, activities,
+      h, "row_violations_panel", false, k, row_lb, row_ub, tolerance, row_starts, rows, activities,
       capacity, summaries, [&](bool lists, bool sums, milp::DeviceLp::RowViolations* out) {
         h->dev.RowViolationsPanel(x, k, row_lb, row_ub, tolerance, lists, sums, out);
       });
@@ -450,8 +451,8 @@ int RowViolationsPanelFrom(mi_devop* h, const double* base, int k, const int64_t
                            int32_t* rows, double* activities, int64_t capacity,
                            mi_devop_point_violations* summaries) {
   return RowViolationsCall(
-      h, "row_violations_panel_from", k, row_lb, row_ub, tolerance, row_starts, rows, activities,
-      capacity, summaries, [&](bool lists, bool sums, milp::DeviceLp::RowViolations* out) {
+      h, "row_violations_panel_from", false, k, row_lb, row_ub, tolerance, row_starts, rows,
+      activities, capacity, summaries, [&](bool lists, bool sums, milp::DeviceLp::RowViolations* out) {
         if (!milp::DeviceLp::ValidOverrides(h->csc.num_cols(), k, starts, cols) ||
             (starts[k] > 0 && vals == nullptr)) {
           throw milp::DeviceError("row_violations_panel_from: bad overrides");
@@ -464,6 +465,74 @@ int RowViolationsPanelFrom(mi_devop* h, const double* base, int k, const int64_t
 int LastRowViolations(mi_devop* h, mi_devop_row_violations* out) {
   return Guard(h, [&] {
     const milp::DeviceLp::LastRowViolations p = h->dev.last_row_violations();
+    out->panels = p.panels;
+    out->width = p.width;
+    out->lists = p.lists ? 1 : 0;
+    out->reserved = 0;
+    out->kept = p.kept;
+    out->bytes_down = p.bytes_down;
+    out->overrides_up_bytes = p.overrides_up_bytes;
+  });
+}
+
+// The structural columns of the handle's matrix: the bound sets' columns.
+int Structural(const mi_devop* h) { return h->csc.num_cols() - h->csc.num_rows(); }
+
+void CheckBoundOverrides(const mi_devop* h, const char* name, int k, const int64_t* starts,
+                         const int32_t* cols, const double* new_lbs, const double* new_ubs) {
+  if (!milp::DeviceLp::ValidOverrides(Structural(h), k, starts, cols) ||
+      (starts[k] > 0 && (new_lbs == nullptr || new_ubs == nullptr))) {
+    throw milp::DeviceError(std::string(name) + ": bad overrides");
+  }
+}
+
+int BoundRangesPanel(mi_devop* h, const double* lbs, const double* ubs, int k,
+                     double* min_activity, double* max_activity, int32_t* inf_counts) {
+  return Guard(h, [&] {
+    h->dev.BoundRangesPanel(lbs, ubs, k, min_activity, max_activity, inf_counts);
+  });
+}
+
+int BoundRangesPanelFrom(mi_devop* h, const double* base_lb, const double* base_ub, int k,
+                         const int64_t* starts, const int32_t* cols, const double* new_lbs,
+                         const double* new_ubs, double* min_activity, double* max_activity,
+                         int32_t* inf_counts) {
+  return Guard(h, [&] {
+    CheckBoundOverrides(h, "bound_ranges_panel_from", k, starts, cols, new_lbs, new_ubs);
+    h->dev.BoundRangesPanelFrom(base_lb, base_ub, k, starts, cols, new_lbs, new_ubs, min_activity,
+                                max_activity, inf_counts);
+  });
+}
+
+int BoundInfeasiblePanel(mi_devop* h, const double* lbs, const double* ubs, int k,
+                         const double* row_lb, const double* row_ub, double tolerance,
+                         int64_t* row_starts, int32_t* rows, double* amounts, int64_t capacity,
+                         mi_devop_point_violations* summaries) {
+  return RowViolationsCall(
+      h, "bound_infeasible_panel", true, k, row_lb, row_ub, tolerance, row_starts, rows, amounts,
+      capacity, summaries, [&](bool lists, bool, milp::DeviceLp::RowViolations* out) {
+        h->dev.BoundInfeasiblePanel(lbs, ubs, k, row_lb, row_ub, tolerance, lists, out);
+      });
+}
+
+int BoundInfeasiblePanelFrom(mi_devop* h, const double* base_lb, const double* base_ub, int k,
+                             const int64_t* starts, const int32_t* cols, const double* new_lbs,
+                             const double* new_ubs, const double* row_lb, const double* row_ub,
+                             double tolerance, int64_t* row_starts, int32_t* rows,
+                             double* amounts, int64_t capacity,
+                             mi_devop_point_violations* summaries) {
+  return RowViolationsCall(
+      h, "bound_infeasible_panel_from", true, k, row_lb, row_ub, tolerance, row_starts, rows,
+      amounts, capacity, summaries, [&](bool lists, bool, milp::DeviceLp::RowViolations* out) {
+        CheckBoundOverrides(h, "bound_infeasible_panel_from", k, starts, cols, new_lbs, new_ubs);
+        h->dev.BoundInfeasiblePanelFrom(base_lb, base_ub, k, starts, cols, new_lbs, new_ubs,
+                                        row_lb, row_ub, tolerance, lists, out);
+      });
+}
+
+int LastBoundRanges(mi_devop* h, mi_devop_row_violations* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastBoundRanges p = h->dev.last_bound_ranges();
     out->panels = p.panels;
     out->width = p.width;
     out->lists = p.lists ? 1 : 0;
@@ -514,4 +583,7 @@ extern "C" const mi_devop_api mi_devop_table = {
     LastRowPanel,     RowPanelGeometry,
     RowViolationsPanel, RowViolationsPanelFrom,
     LastRowViolations,
+    BoundRangesPanel, BoundRangesPanelFrom,
+    BoundInfeasiblePanel, BoundInfeasiblePanelFrom,
+    LastBoundRanges,
 };

@@ -5720,6 +5720,10 @@ struct mi_lp {
   // built them (its summaries are not kept).
   milp::DeviceLp::RowViolations violated_rows;
   bool violated_rows_stored = false;
+  // Likewise the lists of the last mi_lp_bound_infeasible_rows(_from) call
+  // that built them (rows and, in `activities`, the amounts).
+  milp::DeviceLp::RowViolations infeasible_rows;
+  bool infeasible_rows_stored = false;
   milp::GlopParameters params;
   milp::LinearProgram lp;
   int device = 0;
@@ -6059,6 +6063,7 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t*
   if (cs[n] > 0 && (ri == nullptr || vals == nullptr)) return MI_LP_ERROR_NULL;
   h->sparse_rows_stored = false;  // mi_lp_get_sparse_rows: rows of the LP before
   h->violated_rows_stored = false;  // mi_lp_get_violated_rows: likewise
+  h->infeasible_rows_stored = false;  // mi_lp_get_infeasible_rows: likewise
   if ((n > 0 && (clb == nullptr || cub == nullptr || obj == nullptr)) ||
       (m > 0 && (rlb == nullptr || rub == nullptr))) {
     return MI_LP_ERROR_NULL;
@@ -6420,11 +6425,12 @@ int CheckViolationArgs(const mi_lp* h, int32_t k, const double** row_lb, const d
 }
 
 // run(lists, summaries, &result) computes; then the outputs are written and,
-// when lists were built, the result becomes the stored one. Nothing is
+// when lists were built, the result becomes the stored one (*store, *stored:
+// the violated rows' or the infeasible rows' store of the handle). Nothing is
 // written or stored unless run returns MI_LP_OK.
 template <typename Run>
-int ViolationsCall(mi_lp* h, int32_t k, int64_t* row_starts, mi_lp_point_violations* summaries,
-                   Run run) {
+int ViolationsCall(mi_lp* h, milp::DeviceLp::RowViolations* store, bool* stored, int32_t k,
+                   int64_t* row_starts, mi_lp_point_violations* summaries, Run run) {
   return PanelCall(h, [&]() -> int {
     milp::DeviceLp::RowViolations result;
     const int bad = run(row_starts != nullptr, summaries != nullptr, &result);
@@ -6433,8 +6439,8 @@ int ViolationsCall(mi_lp* h, int32_t k, int64_t* row_starts, mi_lp_point_violati
     if (row_starts != nullptr) {
       std::copy(result.row_starts.begin(), result.row_starts.end(), row_starts);
       result.summaries.clear();
-      h->violated_rows = std::move(result);
-      h->violated_rows_stored = true;
+      *store = std::move(result);
+      *stored = true;
     }
     return MI_LP_OK;
   });
@@ -6452,7 +6458,7 @@ int mi_lp_column_combinations_violations(mi_lp* h, const double* x, int32_t k,
   }
   const int bad = CheckViolationArgs(h, k, &row_lb, &row_ub, tolerance);
   if (bad != MI_LP_OK) return bad;
-  return ViolationsCall(h, k, row_starts, summaries,
+  return ViolationsCall(h, &h->violated_rows, &h->violated_rows_stored, k, row_starts, summaries,
                         [&](bool lists, bool with_summaries, milp::DeviceLp::RowViolations* out) {
                           h->simplex.device().RowViolationsPanel(x, k, row_lb, row_ub, tolerance,
                                                                  lists, with_summaries, out);
@@ -6473,7 +6479,7 @@ int mi_lp_column_combinations_from_violations(mi_lp* h, const double* base, int3
   const int bad = CheckViolationArgs(h, k, &row_lb, &row_ub, tolerance);
   if (bad != MI_LP_OK) return bad;
   return ViolationsCall(
-      h, k, row_starts, summaries,
+      h, &h->violated_rows, &h->violated_rows_stored, k, row_starts, summaries,
       [&](bool lists, bool with_summaries, milp::DeviceLp::RowViolations* out) -> int {
         // As mi_lp_column_combinations_from: starts[k] is read only once the
         // entries before it are known to ascend from 0.
@@ -6498,6 +6504,136 @@ int mi_lp_get_violated_rows(const mi_lp* h, int32_t* rows, double* activities) {
   if (kept > 0) {
     std::memcpy(rows, h->violated_rows.rows.data(), kept * sizeof(int32_t));
     std::memcpy(activities, h->violated_rows.activities.data(), kept * sizeof(double));
+  }
+  return MI_LP_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The override lists of the bound-set calls: columns over the n structural
+// columns, two value arrays. starts[k] is read only once the entries before
+// it are known to ascend from 0.
+int CheckBoundOverrides(const mi_lp* h, int32_t k, const int64_t* starts, const int32_t* cols,
+                        const double* new_lbs, const double* new_ubs) {
+  if (starts[0] != 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  for (int32_t j = 0; j < k; ++j) {
+    if (starts[j + 1] < starts[j]) return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  if (starts[k] > 0 && (cols == nullptr || new_lbs == nullptr || new_ubs == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!milp::DeviceLp::ValidOverrides(h->lp.n, k, starts, cols)) {
+    return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  return MI_LP_OK;
+}
+
+// The argument checks the two screening calls share; MI_LP_OK when they
+// pass. A NULL bound array becomes the loaded one; +-inf is allowed on
+// either side, a NaN is not.
+int CheckScreeningArgs(const mi_lp* h, int32_t k, const double** row_lb, const double** row_ub,
+                       double tolerance) {
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0 || !(tolerance >= 0.0) || std::isinf(tolerance)) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (*row_lb == nullptr) *row_lb = h->lp.row_lb.data();
+  if (*row_ub == nullptr) *row_ub = h->lp.row_ub.data();
+  for (int r = 0; r < h->lp.m; ++r) {
+    if ((*row_lb)[r] != (*row_lb)[r] || (*row_ub)[r] != (*row_ub)[r]) {
+      return MI_LP_ERROR_INVALID_PROBLEM;
+    }
+  }
+  return MI_LP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mi_lp_bound_activity_ranges(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                                double* min_activity, double* max_activity,
+                                int32_t* inf_counts) {
+  if (h == nullptr || lbs == nullptr || ubs == nullptr || min_activity == nullptr ||
+      max_activity == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&] {
+    h->simplex.device().BoundRangesPanel(lbs, ubs, k, min_activity, max_activity, inf_counts);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_bound_activity_ranges_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                     int32_t k, const int64_t* starts, const int32_t* cols,
+                                     const double* new_lbs, const double* new_ubs,
+                                     double* min_activity, double* max_activity,
+                                     int32_t* inf_counts) {
+  if (h == nullptr || base_lb == nullptr || base_ub == nullptr || starts == nullptr ||
+      min_activity == nullptr || max_activity == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&]() -> int {
+    const int bad = CheckBoundOverrides(h, k, starts, cols, new_lbs, new_ubs);
+    if (bad != MI_LP_OK) return bad;
+    h->simplex.device().BoundRangesPanelFrom(base_lb, base_ub, k, starts, cols, new_lbs, new_ubs,
+                                             min_activity, max_activity, inf_counts);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_bound_infeasible_rows(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                                const double* row_lb, const double* row_ub, double tolerance,
+                                int64_t* row_starts, mi_lp_point_violations* summaries) {
+  if (h == nullptr || lbs == nullptr || ubs == nullptr ||
+      (row_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  return ViolationsCall(h, &h->infeasible_rows, &h->infeasible_rows_stored, k, row_starts,
+                        summaries, [&](bool lists, bool, milp::DeviceLp::RowViolations* out) {
+                          h->simplex.device().BoundInfeasiblePanel(lbs, ubs, k, row_lb, row_ub,
+                                                                   tolerance, lists, out);
+                          return int{MI_LP_OK};
+                        });
+}
+
+int mi_lp_bound_infeasible_rows_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                     int32_t k, const int64_t* starts, const int32_t* cols,
+                                     const double* new_lbs, const double* new_ubs,
+                                     const double* row_lb, const double* row_ub,
+                                     double tolerance, int64_t* row_starts,
+                                     mi_lp_point_violations* summaries) {
+  if (h == nullptr || base_lb == nullptr || base_ub == nullptr || starts == nullptr ||
+      (row_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  return ViolationsCall(
+      h, &h->infeasible_rows, &h->infeasible_rows_stored, k, row_starts, summaries,
+      [&](bool lists, bool, milp::DeviceLp::RowViolations* out) -> int {
+        const int bad_overrides = CheckBoundOverrides(h, k, starts, cols, new_lbs, new_ubs);
+        if (bad_overrides != MI_LP_OK) return bad_overrides;
+        h->simplex.device().BoundInfeasiblePanelFrom(base_lb, base_ub, k, starts, cols, new_lbs,
+                                                     new_ubs, row_lb, row_ub, tolerance, lists,
+                                                     out);
+        return MI_LP_OK;
+      });
+}
+
+int mi_lp_get_infeasible_rows(const mi_lp* h, int32_t* rows, double* amounts) {
+  if (h == nullptr || rows == nullptr || amounts == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->infeasible_rows_stored) return MI_LP_ERROR_STATE;
+  const size_t kept = h->infeasible_rows.rows.size();
+  if (kept > 0) {
+    std::memcpy(rows, h->infeasible_rows.rows.data(), kept * sizeof(int32_t));
+    std::memcpy(amounts, h->infeasible_rows.activities.data(), kept * sizeof(double));
   }
   return MI_LP_OK;
 }

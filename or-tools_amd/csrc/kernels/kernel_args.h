@@ -139,12 +139,18 @@ struct PointViolations {  // mi_lp_point_violations of include/mi_lp.h
   int32_t worst_row;
   int32_t reserved;
 };
+//
+// The same passes serve the bound sets' screening (activity_ranges_panel
+// below) under the second rule: `in` then holds g per (row, child), row r
+// proves child v infeasible when g > tolerance, and its amount is g (> 0,
+// never NaN). row_lb / row_ub are not read under that rule.
+enum PanelRowRule { kRowRuleOutsideBounds = 0, kRowRuleAboveTolerance = 1 };
 struct RowViolationArgs {
-  const double* in;      // interleaved row sums, num_rows x K
+  const double* in;      // interleaved row sums (or g), num_rows x K
   int num_rows;
   int kp;                // points in use (<= K)
   int tiles;             // ceil(num_rows / kPanelTileColumns)
-  const double* row_lb;  // num_rows
+  const double* row_lb;  // num_rows (kRowRuleOutsideBounds)
   const double* row_ub;
   double tolerance;
   int* counts;           // kp x tiles
@@ -155,6 +161,33 @@ struct RowViolationArgs {
   PointViolations* summaries;  // kp, or nullptr: no fold
   int32_t* rows;         // packed output, or nullptr: no offsets and no write pass
   double* activities;
+};
+
+// Activity ranges of the rows of A under a panel of K bound sets
+// (panel_kernels.hip, activity_ranges_panel; include/mi_lp.h
+// mi_lp_bound_activity_ranges has the rule). The bounds are two
+// column-interleaved arrays over the num_structural columns,
+// lower[col * K + v] and upper[col * K + v], 0.0 for the padding children
+// v >= kp; entries of a CSR row with col >= num_structural (the slack) are
+// skipped. Per (row, child) two sums from +0.0 in increasing column order and
+// two counts of infinite bounds. Both arrays hold at least one element.
+//   row_lb == nullptr  out receives three row-interleaved blocks of
+//                      num_rows x K 8-byte words: lo, hi, and the counts
+//                      packed as lo_inf | hi_inf << 32.
+//   row_lb != nullptr  out receives g per (row, child) only: num_rows x K
+//                      (the input of the kRowRuleAboveTolerance passes).
+struct ActivityRangeArgs {
+  const int64_t* t_starts;  // CSR of [A | I]
+  const int32_t* t_cols;
+  const double* t_vals;
+  const double* lower;
+  const double* upper;
+  int num_rows;
+  int num_structural;
+  int kp;                // children in use (<= K)
+  const double* row_lb;  // num_rows each, or both nullptr
+  const double* row_ub;
+  double* out;
 };
 
 // Where an update-row kernel that emits the list itself puts it: the
@@ -550,9 +583,13 @@ hipError_t panel_override(int width, const milp_kernels::RowPanelOverrideArgs& a
                           int64_t num_overrides, hipStream_t s);
 // After row_sums_panel on the same stream: violations_count, then (rows !=
 // nullptr) panel_offsets, (summaries != nullptr) violations_fold, and (rows
-// != nullptr) violations_write.
-hipError_t row_violations_panel(int width, const milp_kernels::RowViolationArgs& args,
+// != nullptr) violations_write, all under `rule` (PanelRowRule).
+hipError_t row_violations_panel(int width, int rule, const milp_kernels::RowViolationArgs& args,
                                 hipStream_t s);
+// Activity ranges for a panel of `width` (1, 4 or 16) bound sets in one pass
+// over the rows of [A | I] (panel_kernels.hip activity_ranges_panel_kernel).
+hipError_t activity_ranges_panel(int width, const milp_kernels::ActivityRangeArgs& args,
+                                 hipStream_t s);
 hipError_t dense_pack(const int64_t* starts, const double* vals, const int32_t* dense_cols,
                       int nd, int m, double* body, double* tail, hipStream_t s);
 hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hipStream_t s);

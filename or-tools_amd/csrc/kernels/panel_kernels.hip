@@ -22,7 +22,10 @@
 // (row_sums_panel_kernel and the kernels that build its interleaved points:
 // interleave, panel_fill, panel_override), follows the sparse form, and its
 // own sparse form (violations_count / violations_fold / violations_write:
-// the rows outside their bounds and one summary per point) comes last.
+// the rows outside their bounds and one summary per point) comes after it.
+// Last, the activity ranges of the rows under a panel of K bound sets
+// (activity_ranges_panel_kernel), whose screening form goes through the same
+// count, fold and write passes under a second rule.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -511,11 +514,44 @@ __device__ __forceinline__ void worst_merge(double* amount, int* row, double oth
   }
 }
 
+// The rule of the count and the write pass and the amount of a kept row, by
+// PanelRowRule: the violated rows of row sums, or the rows whose g (formed by
+// activity_ranges_panel_kernel) exceeds the tolerance. g is never NaN and a
+// kept g is > tolerance >= 0, so worst_merge's (0.0, kNoWorstRow) start
+// serves both.
+template <int RULE>
+struct RowRule;
+template <>
+struct RowRule<kRowRuleOutsideBounds> {
+  static __device__ __forceinline__ bool keep(const RowViolationArgs& a, double x, int row,
+                                              double* amount) {
+    const double lo = a.row_lb[row];
+    const double hi = a.row_ub[row];
+    if (!row_violated(x, lo, hi, a.tolerance)) return false;
+    *amount = violation_amount(x, lo, hi);
+    return true;
+  }
+  static __device__ __forceinline__ bool keep(const RowViolationArgs& a, double x, int row) {
+    return row_violated(x, a.row_lb[row], a.row_ub[row], a.tolerance);
+  }
+};
+template <>
+struct RowRule<kRowRuleAboveTolerance> {
+  static __device__ __forceinline__ bool keep(const RowViolationArgs& a, double x, int,
+                                              double* amount) {
+    *amount = x;
+    return x > a.tolerance;
+  }
+  static __device__ __forceinline__ bool keep(const RowViolationArgs& a, double x, int) {
+    return x > a.tolerance;
+  }
+};
+
 // panel_count_kernel's tile and thread layout: thread t reads elements t,
 // t + 256, ... of the tile's 256 * K contiguous doubles and meets one point
 // only, v = t % K, at rows t / K + j * (256 / K), ascending in j. The lanes
 // of a point combine by shuffles, the four waves through LDS.
-template <int K>
+template <int K, int RULE>
 __global__ __launch_bounds__(kPanelTileColumns) void violations_count_kernel(
     RowViolationArgs a) {
   static_assert(kPanelTileColumns == 256 && kPanelTileColumns % K == 0 && kWave % K == 0,
@@ -539,11 +575,10 @@ __global__ __launch_bounds__(kPanelTileColumns) void violations_count_kernel(
       const int rl = t / K + j * (kPanelTileColumns / K);
       if (rl < rows) {
         const double x = in[t + j * kPanelTileColumns];
-        const double lo = a.row_lb[row0 + rl];
-        const double hi = a.row_ub[row0 + rl];
-        if (row_violated(x, lo, hi, a.tolerance)) {
+        double row_amount;
+        if (RowRule<RULE>::keep(a, x, row0 + rl, &row_amount)) {
           ++c;
-          worst_merge(&amount, &worst_row, violation_amount(x, lo, hi), row0 + rl);
+          worst_merge(&amount, &worst_row, row_amount, row0 + rl);
         }
       }
     }
@@ -625,18 +660,112 @@ __global__ __launch_bounds__(kPanelOffsetsStep) void violations_fold_kernel(RowV
   }
 }
 
-// panel_write_kernel's pass with the violation rule: rows[offset + rank] and
-// activities[offset + rank] in increasing row order.
-template <int K>
+// panel_write_kernel's pass with the rule: rows[offset + rank] and
+// activities[offset + rank] (the kept element of `in`: the activity, or g,
+// which is its own amount) in increasing row order.
+template <int K, int RULE>
 __global__ __launch_bounds__(kPanelTileColumns) void violations_write_kernel(
     RowViolationArgs a) {
   __shared__ double tile_vals[K * panel_write_stride<K>()];
   panel_write_tile<K>(
       a.in, a.num_rows, a.kp, a.tiles, a.offsets,
-      [&a](double x, int row) {
-        return row_violated(x, a.row_lb[row], a.row_ub[row], a.tolerance);
-      },
-      a.rows, a.activities, tile_vals);
+      [&a](double x, int row) { return RowRule<RULE>::keep(a, x, row); }, a.rows, a.activities,
+      tile_vals);
+}
+
+// ---------------------------------------------------------------------------
+// Activity ranges of the rows of A under a panel of K bound sets in one pass
+// over the rows (include/mi_lp.h mi_lp_bound_activity_ranges; the argument
+// block says what is stored). row_sums_panel_kernel's shape: thread t owns
+// (row t / K, child t % K), the K lanes of a row are adjacent, the row is
+// walked strictly in order and the gathers of kRowPanelUnroll entries are
+// issued ahead of the ordered adds; no barrier and no cross-lane step. An
+// entry meets two contiguous reads of K doubles, L[col * K ..] and
+// U[col * K ..]; which of them feeds the minimum depends on the sign of the
+// entry, which is one value for the K lanes of a row but not for a wave, so
+// it is a select and not a branch. The slack entry (col >= num_structural),
+// a zero coefficient and an infinite bound are added as -0.0, which leaves
+// every sum's bits unchanged, and the counts are incremented by the
+// predicate: the lanes stay converged. The slack's gather is redirected to
+// column 0 (the bound arrays end at num_structural columns).
+__device__ __forceinline__ void activity_range_term(double a, double l, double u, bool structural,
+                                                    double* lo, double* hi, int* lo_inf,
+                                                    int* hi_inf) {
+  const bool up = a > 0.0;  // false for a NaN coefficient: the else branch of the rule
+  const double bl = up ? l : u;
+  const double bh = up ? u : l;
+  const bool live = structural && a != 0.0;
+  const bool lo_is_inf = fabs(bl) == __builtin_inf();
+  const bool hi_is_inf = fabs(bh) == __builtin_inf();
+  *lo += (live && !lo_is_inf) ? a * bl : -0.0;
+  *hi += (live && !hi_is_inf) ? a * bh : -0.0;
+  *lo_inf += (live && lo_is_inf) ? 1 : 0;
+  *hi_inf += (live && hi_is_inf) ? 1 : 0;
+}
+
+template <int K>
+__global__ __launch_bounds__(kRowPanelThreads) void activity_ranges_panel_kernel(
+    ActivityRangeArgs a) {
+  static_assert(kRowPanelThreads % K == 0, "whole rows per workgroup");
+  constexpr int kRows = kRowPanelThreads / K;
+  const int v = threadIdx.x % K;
+  const int row = blockIdx.x * kRows + threadIdx.x / K;
+  if (row >= a.num_rows) return;  // no barrier and no cross-lane step below
+  const int64_t s = a.t_starts[row];
+  const int64_t e = a.t_starts[row + 1];
+  const int n = a.num_structural;
+  const double* __restrict__ lower = a.lower + v;
+  const double* __restrict__ upper = a.upper + v;
+  double lo = 0.0;
+  double hi = 0.0;
+  int lo_inf = 0;
+  int hi_inf = 0;
+  int64_t i = s;
+  for (; i + kRowPanelUnroll <= e; i += kRowPanelUnroll) {
+    int col[kRowPanelUnroll];
+    double val[kRowPanelUnroll];
+    double l[kRowPanelUnroll];
+    double u[kRowPanelUnroll];
+#pragma unroll
+    for (int j = 0; j < kRowPanelUnroll; ++j) {
+      col[j] = a.t_cols[i + j];
+      val[j] = a.t_vals[i + j];
+    }
+#pragma unroll
+    for (int j = 0; j < kRowPanelUnroll; ++j) {
+      const int64_t at = static_cast<int64_t>(col[j] < n ? col[j] : 0) * K;
+      l[j] = lower[at];
+      u[j] = upper[at];
+    }
+#pragma unroll
+    for (int j = 0; j < kRowPanelUnroll; ++j) {
+      activity_range_term(val[j], l[j], u[j], col[j] < n, &lo, &hi, &lo_inf, &hi_inf);
+    }
+  }
+  for (; i < e; ++i) {
+    const int col = a.t_cols[i];
+    const int64_t at = static_cast<int64_t>(col < n ? col : 0) * K;
+    activity_range_term(a.t_vals[i], lower[at], upper[at], col < n, &lo, &hi, &lo_inf, &hi_inf);
+  }
+  if (v >= a.kp) return;
+  const int64_t at = static_cast<int64_t>(row) * K + v;
+  if (a.row_lb != nullptr) {
+    // Each difference is one rounded operation; a NaN difference fails the
+    // comparison and never replaces g.
+    double g = -__builtin_inf();
+    const double over = lo - a.row_ub[row];
+    const double under = a.row_lb[row] - hi;
+    if (lo_inf == 0 && over > g) g = over;
+    if (hi_inf == 0 && under > g) g = under;
+    a.out[at] = g;
+  } else {
+    const int64_t block = static_cast<int64_t>(a.num_rows) * K;
+    a.out[at] = lo;
+    a.out[block + at] = hi;
+    reinterpret_cast<unsigned long long*>(a.out)[2 * block + at] =
+        static_cast<unsigned long long>(static_cast<unsigned int>(lo_inf)) |
+        (static_cast<unsigned long long>(static_cast<unsigned int>(hi_inf)) << 32);
+  }
 }
 
 }  // namespace milp_kernels
@@ -712,12 +841,39 @@ hipError_t row_sums_panel(int width, const RowPanelArgs& args, hipStream_t s) {
   });
 }
 
-hipError_t row_violations_panel(int width, const RowViolationArgs& args, hipStream_t s) {
+hipError_t activity_ranges_panel(int width, const ActivityRangeArgs& args, hipStream_t s) {
   if (args.num_rows <= 0 || args.kp <= 0) return hipSuccess;
-  if (args.tiles != panel_div_up(args.num_rows, kPanelTileColumns)) return hipErrorInvalidValue;
+  if ((args.row_lb == nullptr) != (args.row_ub == nullptr)) return hipErrorInvalidValue;
   return for_panel_width(width, [&](auto w) {
     constexpr int K = decltype(w)::value;
-    violations_count_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+    const int blocks = panel_div_up(args.num_rows, kRowPanelThreads / K);
+    activity_ranges_panel_kernel<K><<<blocks, kRowPanelThreads, 0, s>>>(args);
+  });
+}
+
+// launch(std::integral_constant<int, RULE>) for a PanelRowRule.
+template <typename Launch>
+static void for_row_rule(int rule, Launch launch) {
+  if (rule == kRowRuleOutsideBounds) {
+    launch(std::integral_constant<int, kRowRuleOutsideBounds>());
+  } else {
+    launch(std::integral_constant<int, kRowRuleAboveTolerance>());
+  }
+}
+
+hipError_t row_violations_panel(int width, int rule, const RowViolationArgs& args,
+                                hipStream_t s) {
+  if (args.num_rows <= 0 || args.kp <= 0) return hipSuccess;
+  if (args.tiles != panel_div_up(args.num_rows, kPanelTileColumns)) return hipErrorInvalidValue;
+  if (rule != kRowRuleOutsideBounds && rule != kRowRuleAboveTolerance) {
+    return hipErrorInvalidValue;
+  }
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    for_row_rule(rule, [&](auto r) {
+      violations_count_kernel<K, decltype(r)::value>
+          <<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+    });
     if (args.rows != nullptr) {
       PanelSparseArgs o{};  // the fields panel_offsets_kernel reads
       o.kp = args.kp;
@@ -731,7 +887,10 @@ hipError_t row_violations_panel(int width, const RowViolationArgs& args, hipStre
       violations_fold_kernel<<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
     }
     if (args.rows != nullptr) {
-      violations_write_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+      for_row_rule(rule, [&](auto r) {
+        violations_write_kernel<K, decltype(r)::value>
+            <<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+      });
     }
   });
 }

@@ -371,6 +371,23 @@ def branch_lps(trail, x, cols):
     return lbs, ubs
 
 
+def branch_overrides(trail, x, cols):
+    """branch_lps as one base and one override per child, for
+    LpHandle.infeasible_rows_from / bound_activity_ranges_from: (base_lb,
+    base_ub, overrides) with overrides[j] = (cols, new_lbs, new_ubs), in
+    branch_lps order. Materialised, it equals branch_lps(trail, x, cols)."""
+    base_lb = np.array(trail.lb, copy=True)
+    base_ub = np.array(trail.ub, copy=True)
+    overrides = []
+    for c in cols:
+        col = np.array([c], np.int32)
+        down = np.array([math.floor(x[c])], base_ub.dtype)
+        up = np.array([math.ceil(x[c])], base_lb.dtype)
+        overrides.append((col, base_lb[[c]], down))
+        overrides.append((col, up, base_ub[[c]]))
+    return base_lb, base_ub, overrides
+
+
 def fold_node(trail, x, cols, results):
     """Folds batched branch results (MiLpResult per branch LP, in branch_lps
     order) with BranchOnVar's decisions, column by column. Returns a summary:

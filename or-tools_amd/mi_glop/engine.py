@@ -132,6 +132,13 @@ def lib():
     L.mi_lp_column_combinations_from_violations.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp,
                                                             vp, vp, ctypes.c_double, vp, vp]
     L.mi_lp_get_violated_rows.argtypes = [vp, vp, vp]
+    L.mi_lp_bound_activity_ranges.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp, vp]
+    L.mi_lp_bound_activity_ranges_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 7
+    L.mi_lp_bound_infeasible_rows.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp,
+                                              ctypes.c_double, vp, vp]
+    L.mi_lp_bound_infeasible_rows_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 6 + [
+        ctypes.c_double, vp, vp]
+    L.mi_lp_get_infeasible_rows.argtypes = [vp, vp, vp]
     L.mi_lp_solver_params_default.argtypes = [ctypes.POINTER(abi.MiLpSolverParams)]
     L.mi_lp_scale.argtypes = [ctypes.POINTER(abi.MiLpSolverParams), ctypes.c_int32,
                               ctypes.c_int32] + [vp] * 14
@@ -694,6 +701,110 @@ class LpHandle:
             "column_combinations_from_violations", k, lists,
             (_p(base), k, _p(starts), _p(cols) if len(cols) else None,
              _p(vals) if len(vals) else None), row_lb, row_ub, tolerance)
+
+    def _bound_sets(self, lbs, ubs):
+        """(lbs, ubs, k): two contiguous (k, n) arrays (1-D for k = 1)."""
+        n = self.lp.n
+        out = []
+        for what, b in (("lbs", lbs), ("ubs", ubs)):
+            b = np.ascontiguousarray(b, dtype=np.float64)
+            if b.ndim == 1:
+                b = b.reshape(1, -1)
+            if b.ndim != 2 or b.shape[1] != n:
+                raise ValueError(f"{what} must be (k, {n}), got {b.shape}")
+            out.append(b)
+        if out[0].shape != out[1].shape:
+            raise ValueError(f"lbs is {out[0].shape}, ubs {out[1].shape}")
+        k = out[0].shape[0]
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            out = [np.zeros((1, max(n, 1)), np.float64)] * 2
+        return out[0], out[1], k
+
+    def _bound_overrides(self, base_lb, base_ub, overrides):
+        """The leading arguments of the override calls after the handle, and k."""
+        base_lb, base_ub, one = self._bound_sets(base_lb, base_ub)
+        if one != 1:
+            raise ValueError("base_lb / base_ub must be one bound set")
+        k = len(overrides)
+        starts = np.zeros(k + 1, np.int64)
+        parts = [[np.zeros(0, np.int32)], [np.zeros(0, np.float64)], [np.zeros(0, np.float64)]]
+        for j, (c, lo, hi) in enumerate(overrides):
+            c = np.ascontiguousarray(c, dtype=np.int32).reshape(-1)
+            lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(-1)
+            hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(-1)
+            if not len(c) == len(lo) == len(hi):
+                raise ValueError(f"overrides[{j}]: {len(c)} columns, {len(lo)} and {len(hi)} bounds")
+            for part, a in zip(parts, (c, lo, hi)):
+                part.append(a)
+            starts[j + 1] = starts[j] + len(c)
+        cols, new_lbs, new_ubs = (np.ascontiguousarray(np.concatenate(p)) for p in parts)
+        some = len(cols) > 0
+        # The arrays are returned too: the pointers must outlive the call.
+        keep = (base_lb, base_ub, starts, cols, new_lbs, new_ubs)
+        args = (_p(base_lb), _p(base_ub), k, _p(starts), _p(cols) if some else None,
+                _p(new_lbs) if some else None, _p(new_ubs) if some else None)
+        return args, k, keep
+
+    def _ranges(self, name, k, args):
+        m = self.lp.m
+        lo = np.zeros((max(k, 1), m), np.float64)
+        hi = np.zeros((max(k, 1), m), np.float64)
+        counts = np.zeros((max(k, 1), m, 2), np.int32)
+        self._call(name, *args, _p(lo), _p(hi), _p(counts))
+        return lo[:k], hi[:k], counts[:k, :, 0].copy(), counts[:k, :, 1].copy()
+
+    def bound_activity_ranges(self, lbs, ubs):
+        """The activity range of every row of A under each of k bound sets over
+        the n structural columns (lbs, ubs: (k, n), as batch_solve_bounds takes
+        them), computed on the GPU with A read once per 16 sets. Returns (lo,
+        hi, lo_inf, hi_inf), each (k, m): the sums of the finite terms and the
+        counts of infinite bounds on each side (include/mi_lp.h
+        mi_lp_bound_activity_ranges has the rule). The minimum of row r under
+        set j is -inf when lo_inf[j, r] > 0, else lo[j, r]."""
+        lbs, ubs, k = self._bound_sets(lbs, ubs)
+        return self._ranges("bound_activity_ranges", k, (_p(lbs), _p(ubs), k))
+
+    def bound_activity_ranges_from(self, base_lb, base_ub, overrides):
+        """bound_activity_ranges of the sets base with l[cols] = new_lbs,
+        u[cols] = new_ubs for overrides[j] = (cols, new_lbs, new_ubs), built on
+        the GPU: only the base bounds and the override lists go up. No column
+        twice within a set."""
+        args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
+        return self._ranges("bound_activity_ranges_from", k, args)
+
+    def _infeasible(self, name, k, lists, args, row_lb, row_ub, tolerance):
+        lb, ub = self._row_bounds(row_lb, "row_lb"), self._row_bounds(row_ub, "row_ub")
+        starts = np.zeros(max(k, 1) + 1, np.int64) if lists else None
+        summaries = np.zeros(max(k, 1), POINT_VIOLATIONS)
+        self._call(name, *args, None if lb is None else _p(lb), None if ub is None else _p(ub),
+                   ctypes.c_double(tolerance), None if starts is None else _p(starts),
+                   _p(summaries))
+        if not lists:
+            return None, None, None, summaries[:k]
+        kept = int(starts[k])
+        rows = np.zeros(max(1, kept), np.int32)
+        amounts = np.zeros(max(1, kept), np.float64)
+        self._call("get_infeasible_rows", _p(rows), _p(amounts))
+        return starts[:k + 1], rows[:kept], amounts[:kept], summaries[:k]
+
+    def infeasible_rows(self, lbs, ubs, row_lb=None, row_ub=None, tolerance=0.0, lists=True):
+        """The rows that prove a bound set infeasible, filtered on the GPU: row
+        r proves set j when its activity range misses [row_lb[r], row_ub[r]]
+        by more than tolerance (g > tolerance, include/mi_lp.h). Conservative:
+        a NaN bound or an overflowed sum only ever gives "not proven". Returns
+        (row_starts, rows, amounts, summaries) shaped like column_violations;
+        with lists=False only the summaries come down."""
+        lbs, ubs, k = self._bound_sets(lbs, ubs)
+        return self._infeasible("bound_infeasible_rows", k, lists, (_p(lbs), _p(ubs), k), row_lb,
+                                row_ub, tolerance)
+
+    def infeasible_rows_from(self, base_lb, base_ub, overrides, row_lb=None, row_ub=None,
+                             tolerance=0.0, lists=True):
+        """infeasible_rows of the sets of bound_activity_ranges_from(base_lb,
+        base_ub, overrides): the children of a node (cpsat.branch_overrides)."""
+        args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
+        return self._infeasible("bound_infeasible_rows_from", k, lists, args, row_lb, row_ub,
+                                tolerance)
 
 
 def batch_solve(handles, num_threads=4, progress=None, progress_s=15.0):
