@@ -524,6 +524,96 @@ int mi_lp_bound_infeasible_rows_from(mi_lp* h, const double* base_lb, const doub
                                      mi_lp_point_violations* summaries);
 int mi_lp_get_infeasible_rows(const mi_lp* h, int32_t* rows, double* amounts);
 
+/* One round of bound propagation over those ranges: from each row's activity
+ * range and bounds, the implied bounds of every structural column it holds,
+ * per bound set, in the same call (the ranges never leave the GPU). Per set j,
+ * with l = lbs[j] and u = ubs[j], let (lo, hi, lo_inf, hi_inf)[r] be row r's
+ * result of mi_lp_bound_activity_ranges, bit for bit, and rlb = row_lb, rub =
+ * row_ub. For every column c < n:
+ *   nl = l[c]; nu = u[c]
+ *   for the entries (r, a) of column c, in any order:
+ *     if a == 0.0 or a is NaN: continue
+ *     up = a > 0.0
+ *     (bl, bh) = (l[c], u[c]) if up else (u[c], l[c])    what c fed into lo / hi
+ *     for (rb, s, cnt, b, tightens_upper) in ((rub[r], lo[r], lo_inf[r], bl, up),
+ *                                             (rlb[r], hi[r], hi_inf[r], bh, !up)):
+ *       if !isfinite(rb): continue
+ *       if   cnt == 0:              res = s - a * b      product and difference
+ *                                                        rounded separately
+ *       elif cnt == 1 and isinf(b): res = s              c is the one infinite term
+ *       else: continue
+ *       q = (rb - res) / a                               one difference, one division
+ *       if !isfinite(q): continue                        NaN and overflow: no candidate
+ *       q = q + 0.0                                      -0.0 becomes +0.0
+ *       if tightens_upper: if q < nu: nu = q
+ *       else:              if q > nl: nl = q
+ * No FMA anywhere. A NaN own bound stays NaN (every comparison with it fails);
+ * otherwise nl >= l and nu <= u. A column without entries keeps its bounds.
+ * Every result is a max or a min of independently rounded candidates, and the
+ * q + 0.0 step gives equal candidates equal bits, so the result does not
+ * depend on the order of the entries or of the GPU's reduction. The rule is
+ * the textbook one in doubles and is NOT outward-rounded: an implied bound can
+ * be off by the rounding of its sum in either direction, and a caller that
+ * needs a safe bound widens it itself. The tolerance below is a filter, not a
+ * safety margin.
+ *   mi_lp_bound_implied_bounds       new_lbs[j n + c] = nl, new_ubs[j n + c] =
+ *                                    nu, k x n each, set-major.
+ *   mi_lp_bound_implied_bounds_from  the same for the sets base + overrides of
+ *                                    mi_lp_bound_activity_ranges_from (ov_lbs /
+ *                                    ov_ubs are its new_lbs / new_ubs). Bit for
+ *                                    bit the dense form on the materialised sets.
+ * The filtered form keeps, per set, with tol = tolerance:
+ *   moved    = (nl - l[c] > tol) || (u[c] - nu > tol)    inf - inf is NaN: no
+ *   cross    = nl - nu;  crossing = cross > tol
+ *   changed  = l[c] or u[c] differs IN BITS from base_lb[c] / base_ub[c]
+ *   dense form: keep iff moved || crossing;  override form: keep iff moved ||
+ *   crossing || changed
+ * so a column whose own bounds already cross is kept without any move, and in
+ * the override form a set's list is its complete override list relative to
+ * the base: fed back unchanged as overrides it gives a second round,
+ * mi_lp_bound_infeasible_rows_from, or the child for mi_lp_batch_solve_bounds.
+ *   lists      col_starts has k+1 entries; set j's entries are its kept
+ *              columns in strictly increasing order, each with nl and nu.
+ *   summaries  mi_lp_point_violations: count the number of kept columns, worst
+ *              the largest cross among the crossing columns (0.0 without one),
+ *              worst_row the lowest COLUMN attaining it (-1 without one; count
+ *              > 0 with worst_row == -1 is the ordinary case). A set is proven
+ *              infeasible by propagation iff worst_row >= 0.
+ *   mi_lp_bound_tightened_columns       compute, store the lists in the handle
+ *   mi_lp_bound_tightened_columns_from  and write col_starts and summaries;
+ *   mi_lp_get_tightened_columns         copies the stored columns and bounds
+ *                                       out, col_starts[k] of each.
+ * NULL handling, k = 0, the state before a solve and every error code are
+ * those of mi_lp_bound_infeasible_rows(_from): row_lb / row_ub may be NULL
+ * (the loaded bounds), +-inf allowed, a NaN row bound is
+ * MI_LP_ERROR_INVALID_PROBLEM, as are a bad tolerance, bad starts and a
+ * repeated column; col_starts == NULL means summaries only, and a previously
+ * stored list stays. The stored lists are a fourth store of the handle; it
+ * neither sees nor disturbs the other three. With MILP_SHARDS the calls stay
+ * on the unsplit handle. No solve uses these calls and they change no state a
+ * later solve reads.
+ * Out of scope: integer rounding of the results (a caller rounds the short
+ * list); more than one round per call; a packed or double2 layout of the
+ * three range blocks; a per-column choice between the two kernel shapes. */
+int mi_lp_bound_implied_bounds(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                               const double* row_lb, const double* row_ub, double* new_lbs,
+                               double* new_ubs);
+int mi_lp_bound_implied_bounds_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                    int32_t k, const int64_t* starts, const int32_t* cols,
+                                    const double* ov_lbs, const double* ov_ubs,
+                                    const double* row_lb, const double* row_ub, double* new_lbs,
+                                    double* new_ubs);
+int mi_lp_bound_tightened_columns(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                                  const double* row_lb, const double* row_ub, double tolerance,
+                                  int64_t* col_starts, mi_lp_point_violations* summaries);
+int mi_lp_bound_tightened_columns_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                       int32_t k, const int64_t* starts, const int32_t* cols,
+                                       const double* ov_lbs, const double* ov_ubs,
+                                       const double* row_lb, const double* row_ub,
+                                       double tolerance, int64_t* col_starts,
+                                       mi_lp_point_violations* summaries);
+int mi_lp_get_tightened_columns(const mi_lp* h, int32_t* cols, double* new_lbs, double* new_ubs);
+
 /* interrupt may be NULL; a non-zero value stops the solve like a time limit
  * (glop_interface.cc:138-140). */
 int mi_lp_solve(mi_lp* h, const volatile int32_t* interrupt, mi_lp_result* out);

@@ -127,6 +127,17 @@ typedef struct mi_devop_row_violations {
   int64_t bytes_down;         /* device-to-host bytes of the call */
   int64_t overrides_up_bytes; /* host-to-device bytes of a row_violations_panel_from call */
 } mi_devop_row_violations;
+/* DeviceLp::LastBoundImplied: the last bound_implied_panel(_from) or
+ * bound_tightened_panel(_from). */
+typedef struct mi_devop_bound_implied {
+  int32_t panels;     /* panels of up to 16 bound sets */
+  int32_t width;      /* padded width of the last panel: 1, 4 or 16 */
+  int32_t columns;    /* MI_DEVOP_PANEL_SHORT_COLUMNS or MI_DEVOP_PANEL_LONG_COLUMNS */
+  int32_t lists;      /* lists were built (col_starts given) */
+  int64_t kept;       /* entries of all sets */
+  int64_t bytes_up;   /* host-to-device bytes of the call: the sets and 16 m of row bounds */
+  int64_t bytes_down; /* device-to-host bytes of the call */
+} mi_devop_bound_implied;
 
 typedef struct mi_devop_api {
   /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
@@ -262,6 +273,38 @@ typedef struct mi_devop_api {
    * 12 kept + 32 k with lists, 24 k for summaries only; overrides_up_bytes:
    * 16 n + 20 overrides + 8 (k + 1) for the override forms. */
   int (*last_bound_ranges)(mi_devop* h, mi_devop_row_violations* out);
+  /* Appended after last_bound_ranges. DeviceLp::BoundImpliedPanel (the rule:
+   * include/mi_lp.h mi_lp_bound_implied_bounds). lbs / ubs and new_lbs /
+   * new_ubs: k x n; row_lb / row_ub: m each, not NULL, no NaN (checked here).
+   * MILP_IMPLIED_COLUMNS = short | long | auto chooses the kernel shape. */
+  int (*bound_implied_panel)(mi_devop* h, const double* lbs, const double* ubs, int k,
+                             const double* row_lb, const double* row_ub, double* new_lbs,
+                             double* new_ubs);
+  /* The sets and their checks as bound_ranges_panel_from. */
+  int (*bound_implied_panel_from)(mi_devop* h, const double* base_lb, const double* base_ub,
+                                  int k, const int64_t* starts, const int32_t* cols,
+                                  const double* ov_lbs, const double* ov_ubs,
+                                  const double* row_lb, const double* row_ub, double* new_lbs,
+                                  double* new_ubs);
+  /* DeviceLp::BoundTightenedPanel in one call. tolerance finite and >= 0
+   * (checked here). col_starts: k + 1; cols / new_lbs / new_ubs: `capacity`
+   * entries; summaries: k, or NULL. col_starts == NULL selects summaries only.
+   * A result of more than `capacity` entries returns MI_DEVOP_CAPACITY
+   * (last_error says how many) with every output unwritten; it is no device
+   * error. */
+  int (*bound_tightened_panel)(mi_devop* h, const double* lbs, const double* ubs, int k,
+                               const double* row_lb, const double* row_ub, double tolerance,
+                               int64_t* col_starts, int32_t* cols, double* new_lbs,
+                               double* new_ubs, int64_t capacity,
+                               mi_devop_point_violations* summaries);
+  int (*bound_tightened_panel_from)(mi_devop* h, const double* base_lb, const double* base_ub,
+                                    int k, const int64_t* starts, const int32_t* cols_in,
+                                    const double* ov_lbs, const double* ov_ubs,
+                                    const double* row_lb, const double* row_ub,
+                                    double tolerance, int64_t* col_starts, int32_t* cols,
+                                    double* new_lbs, double* new_ubs, int64_t capacity,
+                                    mi_devop_point_violations* summaries);
+  int (*last_bound_implied)(mi_devop* h, mi_devop_bound_implied* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

@@ -332,6 +332,62 @@ class DeviceLp : public DeviceSolver {
   using LastBoundRanges = LastRowViolations;
   LastBoundRanges last_bound_ranges() const;
 
+  // --- implied column bounds of k bound sets: one round of propagation over
+  // the activity ranges (include/mi_lp.h mi_lp_bound_implied_bounds has the
+  // rule) -----
+  // The bound sets travel and the ranges are formed exactly as by
+  // BoundRangesPanel(From) (one code path, the dense mode of
+  // activity_ranges_panel_kernel); the ranges stay in the workspace and
+  // implied_bounds_panel_kernel walks the CSC of the n structural columns
+  // over them. row_lb / row_ub: m values, host, uploaded once per call.
+  // new_lbs / new_ubs: k x n, vector-major. Writes nothing a solve reads;
+  // with column shards it stays on the unsplit handle; kernel time is in
+  // TakePanelKernelMs. Synchronizes before it returns.
+  void BoundImpliedPanel(const double* lbs, const double* ubs, int k, const double* row_lb,
+                         const double* row_ub, double* new_lbs, double* new_ubs);
+  void BoundImpliedPanelFrom(const double* base_lb, const double* base_ub, int k,
+                             const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                             const double* ov_ubs, const double* row_lb, const double* row_ub,
+                             double* new_lbs, double* new_ubs);
+  // The filtered form: the kernel also stores one key per (column, child),
+  // and the count, offsets, fold and write passes of the row violations keep
+  // the columns that moved by more than the tolerance, that cross, or (From)
+  // whose own bounds differ in bits from the base; a gather brings the two
+  // bounds to the kept positions. The summaries are always built: per panel
+  // the kp summaries, and with lists the kp totals and the kept (4-byte
+  // column, two 8-byte bounds) entries come down.
+  struct TightenedColumns {
+    std::vector<int64_t> col_starts;  // k + 1 (lists)
+    std::vector<int32_t> cols;        // col_starts[k], ascending per set
+    std::vector<double> new_lbs;
+    std::vector<double> new_ubs;
+    std::vector<mi_lp_point_violations> summaries;  // k
+  };
+  void BoundTightenedPanel(const double* lbs, const double* ubs, int k, const double* row_lb,
+                           const double* row_ub, double tolerance, bool lists,
+                           TightenedColumns* out);
+  void BoundTightenedPanelFrom(const double* base_lb, const double* base_ub, int k,
+                               const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                               const double* ov_ubs, const double* row_lb, const double* row_ub,
+                               double tolerance, bool lists, TightenedColumns* out);
+  // The last of these four calls (test record). columns: the kernel shape,
+  // kPanelShortColumns or kPanelLongColumns (long when the structural
+  // entries per structural column are >= 32; MILP_IMPLIED_COLUMNS = short |
+  // long | auto, read at every call, forces one). bytes_up: 16 k n for the
+  // dense sets or 16 n + 20 overrides + 8 (k + 1) for the override forms,
+  // plus 16 m of row bounds. bytes_down: 16 k n for the dense results,
+  // 20 kept + 32 k with lists, 24 k for summaries only.
+  struct LastBoundImplied {
+    int panels = 0;
+    int width = 0;               // of the last panel
+    int columns = kPanelNone;    // shape of the last panel
+    bool lists = false;          // lists were built
+    int64_t kept = 0;            // entries of all sets
+    int64_t bytes_up = 0;
+    int64_t bytes_down = 0;
+  };
+  LastBoundImplied last_bound_implied() const;
+
   // --- dual device mode: device-resident reduced costs ------------------
   // (see simplex.cc RevisedSimplex::DualDeviceMode). colbits: one byte per
   // column (kernel_args.h kCol*), bound_diff: upper - lower per column.
@@ -577,7 +633,7 @@ class DeviceLp : public DeviceSolver {
     int sparse_cols = 0;
   };
   PanelPlan PanelKernelChoice() const;
-  void PanelReserve(int width, int kp, bool ranges = false);
+  void PanelReserve(int width, int kp, bool ranges = false, bool implied = false);
   void PanelUploadVectors(const double* y, int first, int kp, int width);
   void PanelLaunchDots(const PanelPlan& plan, int kp, int width);
   void PanelRecord(const PanelPlan& plan, int width, LastPanel* record) const;
@@ -596,6 +652,14 @@ class DeviceLp : public DeviceSolver {
     bool ranges = false;
     double* max_activity = nullptr;  // dense ranges: k x m (sums takes the minima)
     int32_t* inf_counts = nullptr;   // dense ranges: k x m x 2, or null
+    // The implied column bounds (with `ranges`): the ranges stay in the
+    // workspace and RowPanelImplied takes over. Dense form: sums / max_activity
+    // take new_lbs / new_ubs (k x n); filtered form: `tightened`, with
+    // tolerance and lists above. from_base: the override form's keep rule.
+    bool implied = false;
+    bool long_columns = false;
+    TightenedColumns* tightened = nullptr;
+    bool from_base = false;
   };
   // upper: the second array of a ranges call (k x n beside x's k x n), else
   // null (x is k x N).
@@ -612,6 +676,14 @@ class DeviceLp : public DeviceSolver {
   // nothing to launch (k <= 0 or no rows).
   bool RowViolationsBegin(LastRowViolations* record, int k, const double* row_lb,
                           const double* row_ub, bool lists, bool summaries, RowViolations* out);
+  // The ranges of one panel are in `rows`: the implied bounds of the panel's
+  // sets, then the dense or the filtered form.
+  void RowPanelImplied(int first, int kp, int width, PanelTimer* timer, const RowPanelSink& sink);
+  // Resets the record and `out` (may be null), uploads the row bounds and
+  // chooses the column shape into `sink`; false when there is nothing to
+  // launch (k <= 0, no rows or no structural columns).
+  bool BoundImpliedBegin(int k, const double* row_lb, const double* row_ub, bool lists,
+                         TightenedColumns* out, RowPanelSink* sink);
   bool is_shard_ = false;
   std::vector<std::unique_ptr<DeviceLp>> shards_;  // null: a block owned by another process
   ExchangeFn exchange_fn_ = nullptr;

@@ -1,7 +1,8 @@
 // The workspace of DeviceLp's panel calls (device_panel.hip): the buffers of
 // ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel, RowSumsPanelFrom,
-// RowViolationsPanel(From), BoundRangesPanel(From) and
-// BoundInfeasiblePanel(From), their timing events and their test records.
+// RowViolationsPanel(From), BoundRangesPanel(From),
+// BoundInfeasiblePanel(From), BoundImpliedPanel(From) and
+// BoundTightenedPanel(From), their timing events and their test records.
 // Included by the HIP translation units only; device_lp.h holds the workspace
 // behind a pointer.
 #ifndef MILP_DEVICE_PANEL_H_
@@ -98,6 +99,18 @@ struct PanelWorkspace {
   // Activity ranges only: the column-interleaved upper bounds, max(1, n)
   // width, read beside `cols` (the lower bounds) by the kernel.
   DeviceBuffer<double> cols_upper;
+  // The implied column bounds (BoundImpliedPanel(From),
+  // BoundTightenedPanel(From)) are an activity-range call in its dense mode
+  // up to the three result blocks in `rows`, which stay there; `cols` and
+  // `cols_upper` still hold the own bounds. implied_bounds_panel_kernel
+  // writes three column-interleaved blocks of max(1, n) width into `implied`:
+  // the new lower bounds, the new upper bounds and (filtered form) the keys.
+  // `flat`, the sets having left it, takes three blocks of kp n: the dense
+  // form's new lower and upper bounds on their way down, or the filtered
+  // form's packed lower bounds, upper bounds and keys (kept_cols beside them).
+  // PanelReserve(ranges, implied) sizes them for that. row_lb / row_ub and,
+  // in the override form, base / base_upper are read as uploaded.
+  DeviceBuffer<double> implied;
   PinnedBuffer<double> y_staging;  // column dots: the host interleave of y, max(1, m width)
 
   // ColumnDotsPanelSparse and the row violations: tiles of 256 columns
@@ -135,6 +148,7 @@ struct PanelWorkspace {
   DeviceLp::LastRowPanel last_row_panel;
   DeviceLp::LastRowViolations last_row_violations;
   DeviceLp::LastBoundRanges last_bound_ranges;
+  DeviceLp::LastBoundImplied last_bound_implied;
 };
 
 }  // namespace milp

@@ -2,13 +2,15 @@
 // Column dots (ColumnDotsPanel, ColumnDotsPanelSparse), row sums (RowSumsPanel,
 // RowSumsPanelFrom), their violated rows (RowViolationsPanel,
 // RowViolationsPanelFrom) and the activity ranges of bound sets
-// (BoundRangesPanel(From), BoundInfeasiblePanel(From)) share one workspace
-// (device_panel.h), one panel loop and one timing scope. No solve calls them
-// and nothing a solve reads is written.
+// (BoundRangesPanel(From), BoundInfeasiblePanel(From)) with the implied column
+// bounds over them (BoundImpliedPanel(From), BoundTightenedPanel(From)) share
+// one workspace (device_panel.h), one panel loop and one timing scope. No
+// solve calls them and nothing a solve reads is written.
 #include "device_panel.h"
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdlib>
 #include <vector>
 
 #include "../kernels/kernel_args.h"
@@ -92,8 +94,9 @@ void DeviceLp::RowPanelGeometry(int rows_per_workgroup[3], int* chunk) {
 // Grows the three shared buffers to one panel of `width` holding `kp`
 // vectors. The stream is idle between panels (each ends with a synchronizing
 // download).
-// ranges: the roles of the activity ranges (device_panel.h).
-void DeviceLp::PanelReserve(int width, int kp, bool ranges) {
+// ranges, implied: the roles of the activity ranges and of the implied column
+// bounds over them (device_panel.h).
+void DeviceLp::PanelReserve(int width, int kp, bool ranges, bool implied) {
   const size_t n = size_t(n_total_ - m_);
   size_t rows = size_t(m_) * width;
   size_t flat = size_t(n_total_) * kp;
@@ -102,6 +105,10 @@ void DeviceLp::PanelReserve(int width, int kp, bool ranges) {
     flat = std::max(flat, std::max(2 * n, 3 * size_t(m_)) * kp);
     // At least one column: the kernel redirects a slack's gather to column 0.
     panel_->cols_upper.Reserve(std::max<size_t>(1, n) * width, "panel upper bounds");
+  }
+  if (implied) {
+    flat = std::max(flat, 3 * n * kp);
+    panel_->implied.Reserve(3 * std::max<size_t>(1, n) * width, "panel implied bounds");
   }
   panel_->rows.Reserve(std::max<size_t>(1, rows), "panel rows");
   panel_->cols.Reserve(size_t(n_total_) * width, "panel columns");
@@ -310,6 +317,7 @@ void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer,
     a.out = w.rows.get();
     Check(milp_launch::row_sums_panel(width, a, S(stream_)), "row sums panel");
   }
+  if (sink.implied) return RowPanelImplied(first, kp, width, timer, sink);
   if (sink.violations != nullptr) return RowPanelViolations(first, kp, width, timer, sink);
   // The dense form: the result blocks of `rows` (one of sums; lo, hi and the
   // packed counts of ranges), each m x width, go vector-major into `flat`.
@@ -354,7 +362,7 @@ void DeviceLp::RowPanels(const double* x, const double* upper, int k, const RowP
   PanelWorkspace& w = *panel_;
   const int ncols = sink.ranges ? n_total_ - m_ : n_total_;
   ForEachPanel(k, [&](int first, int kp, int width) {
-    PanelReserve(width, kp, sink.ranges);
+    PanelReserve(width, kp, sink.ranges, sink.implied);
     const size_t up = size_t(kp) * ncols;
     Upload(w.flat.get(), x + size_t(first) * ncols, up * sizeof(double));
     if (sink.ranges) Upload(w.flat.get() + up, upper + size_t(first) * ncols, up * sizeof(double));
@@ -408,7 +416,7 @@ int64_t DeviceLp::RowPanelsFrom(const double* base, const double* base_upper, in
           "row panel overrides");
   };
   ForEachPanel(k, [&](int first, int kp, int width) {
-    PanelReserve(width, kp, sink.ranges);
+    PanelReserve(width, kp, sink.ranges, sink.implied);
     PanelTimer timer(&w, S(stream_));
     build(w.base.get(), w.ov_vals.get(), w.cols.get(), first, kp, width);
     if (sink.ranges) {
@@ -669,6 +677,245 @@ void DeviceLp::BoundInfeasiblePanelFrom(const double* base_lb, const double* bas
   panel_->last_bound_ranges.overrides_up_bytes =
       RowPanelsFrom(base_lb, base_ub, k, starts, cols, new_lbs, new_ubs, sink);
   DeviceOp("bound infeasible panel from done");
+}
+
+DeviceLp::LastBoundImplied DeviceLp::last_bound_implied() const {
+  return panel_->last_bound_implied;
+}
+
+// The ranges of one panel (lo, hi, packed counts) are in `rows` and the own
+// bounds in `cols` / `cols_upper`: the implied bounds into `implied`; then
+// the dense form (vector-major into `flat`, down to sink.sums and
+// sink.max_activity) or the filtered form (count, offsets, fold and write
+// over the keys, a gather of the two bounds at the kept columns; down come
+// the kp summaries and, with lists, the kp totals and exactly the kept
+// entries, appended set-major).
+void DeviceLp::RowPanelImplied(int first, int kp, int width, PanelTimer* timer,
+                               const RowPanelSink& sink) {
+  PanelWorkspace& w = *panel_;
+  LastBoundImplied& record = w.last_bound_implied;
+  const int n = n_total_ - m_;
+  const size_t block = size_t(n) * width;
+  const size_t down = size_t(kp) * n;
+  TightenedColumns* out = sink.tightened;
+  milp_kernels::ImpliedBoundsArgs a{};
+  a.starts = d_starts_;
+  a.rows = d_rows_;
+  a.vals = d_vals_;
+  a.ranges = w.rows.get();
+  a.row_lb = w.row_lb.get();
+  a.row_ub = w.row_ub.get();
+  a.lower = w.cols.get();
+  a.upper = w.cols_upper.get();
+  a.num_rows = m_;
+  a.num_cols = n;
+  a.kp = kp;
+  a.tolerance = sink.tolerance;
+  if (out != nullptr && sink.from_base) {
+    a.base_lb = w.base.get();
+    a.base_ub = w.base_upper.get();
+  }
+  a.new_lower = w.implied.get();
+  a.new_upper = w.implied.get() + block;
+  a.keys = out != nullptr ? w.implied.get() + 2 * block : nullptr;
+  Check(milp_launch::implied_bounds_panel(width, sink.long_columns, a, S(stream_)),
+        "implied bounds panel");
+  record.panels += 1;
+  record.width = width;
+  record.columns = sink.long_columns ? kPanelLongColumns : kPanelShortColumns;
+  if (out == nullptr) {
+    Check(milp_launch::panel_deinterleave(width, a.new_lower, n, kp, w.flat.get(), n, S(stream_)),
+          "implied bounds de-interleave");
+    Check(milp_launch::panel_deinterleave(width, a.new_upper, n, kp, w.flat.get() + down, n,
+                                          S(stream_)),
+          "implied bounds de-interleave");
+    timer->Launched();
+    Check(hipMemcpyAsync(sink.max_activity + size_t(first) * n, w.flat.get() + down,
+                         down * sizeof(double), hipMemcpyDeviceToHost, S(stream_)),
+          "D2H");
+    Download(sink.sums + size_t(first) * n, w.flat.get(), down * sizeof(double));
+    timer->Downloaded();
+    record.bytes_down += 16 * int64_t(down);
+    return;
+  }
+  const int tiles = (n + milp_kernels::kPanelTileColumns - 1) / milp_kernels::kPanelTileColumns;
+  w.counts.Reserve(size_t(kp) * tiles, "panel counts");
+  w.tile_worst.Reserve(size_t(kp) * tiles, "panel tile worst");
+  w.tile_worst_row.Reserve(size_t(kp) * tiles, "panel tile worst row");
+  milp_kernels::RowViolationArgs v{};
+  v.in = a.keys;
+  v.num_rows = n;
+  v.kp = kp;
+  v.tiles = tiles;
+  v.counts = w.counts.get();
+  v.tile_worst = w.tile_worst.get();
+  v.tile_worst_row = w.tile_worst_row.get();
+  const int64_t* totals = nullptr;
+  if (sink.lists) {
+    w.kept_cols.Reserve(size_t(n) * kp, "panel kept columns");
+    w.offsets.Reserve(size_t(kp) * tiles + milp_kernels::kPanelMaxWidth, "panel offsets");
+    totals = w.totals.Reserve(milp_kernels::kPanelMaxWidth, "panel totals");
+    v.offsets = w.offsets.get();
+    v.totals = w.offsets.get() + size_t(kp) * tiles;
+    v.rows = w.kept_cols.get();
+    v.activities = w.flat.get() + 2 * down;  // the kept keys; not brought down
+  }
+  v.summaries = w.summaries.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
+  const milp_kernels::PointViolations* host_summaries =
+      w.summaries_host.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
+  Check(milp_launch::row_violations_panel(width, milp_kernels::kRowRuleKeptKey, v, S(stream_)),
+        "tightened columns panel");
+  if (sink.lists) {
+    milp_kernels::ImpliedGatherArgs g{};
+    g.totals = v.totals;
+    g.cols = v.rows;
+    g.new_lower = a.new_lower;
+    g.new_upper = a.new_upper;
+    g.num_cols = n;
+    g.kp = kp;
+    g.out_lower = w.flat.get();
+    g.out_upper = w.flat.get() + down;
+    Check(milp_launch::implied_gather(width, g, S(stream_)), "tightened columns gather");
+  }
+  timer->Launched();
+  Download(w.summaries_host.get(), v.summaries, size_t(kp) * sizeof(*v.summaries));
+  for (int c = 0; c < kp; ++c) {
+    const milp_kernels::PointViolations& s = host_summaries[c];
+    if (s.count < 0 || s.count > n || s.worst_row < -1 || s.worst_row >= n) {
+      throw DeviceError("tightened columns panel: bad summary");
+    }
+    mi_lp_point_violations& d = out->summaries[first + c];
+    d.count = s.count;
+    d.worst = s.worst;
+    d.worst_row = s.worst_row;
+    d.reserved = 0;
+  }
+  record.bytes_down += int64_t(kp) * 24;
+  if (sink.lists) {
+    Download(w.totals.get(), v.totals, size_t(kp) * sizeof(int64_t));
+    int64_t kept = 0;
+    for (int c = 0; c < kp; ++c) {
+      if (totals[c] < 0 || totals[c] > n) throw DeviceError("tightened columns panel: bad count");
+      kept += totals[c];
+      out->col_starts[first + c + 1] = out->col_starts[first + c] + totals[c];
+    }
+    const size_t old = out->cols.size();
+    out->cols.resize(old + size_t(kept));
+    out->new_lbs.resize(old + size_t(kept));
+    out->new_ubs.resize(old + size_t(kept));
+    if (kept > 0) {
+      Check(hipMemcpyAsync(out->cols.data() + old, v.rows, size_t(kept) * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+      Check(hipMemcpyAsync(out->new_ubs.data() + old, w.flat.get() + down,
+                           size_t(kept) * sizeof(double), hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+      Download(out->new_lbs.data() + old, w.flat.get(), size_t(kept) * sizeof(double));
+    }
+    record.kept += kept;
+    record.bytes_down += int64_t(kp) * 8 + kept * 20;
+  }
+  timer->Downloaded();
+}
+
+bool DeviceLp::BoundImpliedBegin(int k, const double* row_lb, const double* row_ub, bool lists,
+                                 TightenedColumns* out, RowPanelSink* sink) {
+  PanelWorkspace& w = *panel_;
+  w.last_bound_implied = LastBoundImplied();
+  w.last_bound_implied.lists = lists;
+  const size_t sets = size_t(std::max(k, 0));
+  if (out != nullptr) {
+    out->col_starts.assign(lists ? sets + 1 : 0, 0);
+    out->cols.clear();
+    out->new_lbs.clear();
+    out->new_ubs.clear();
+    out->summaries.assign(sets, mi_lp_point_violations{0, 0.0, -1, 0});
+  }
+  const int n = n_total_ - m_;
+  if (k <= 0 || m_ <= 0 || n <= 0) return false;
+  Upload(w.row_lb.Reserve(size_t(m_), "panel row lower bounds"), row_lb,
+         size_t(m_) * sizeof(double));
+  Upload(w.row_ub.Reserve(size_t(m_), "panel row upper bounds"), row_ub,
+         size_t(m_) * sizeof(double));
+  w.last_bound_implied.bytes_up = 16 * int64_t(m_);
+  // Long columns when the structural entries per structural column are >= 32.
+  // PanelKernelChoice's average leaves the dense block's columns out.
+  bool long_columns = double(h_starts_[n]) / n >= 32.0;
+  if (const char* env = std::getenv("MILP_IMPLIED_COLUMNS")) {
+    const std::string shape(env);
+    if (shape == "short") long_columns = false;
+    if (shape == "long") long_columns = true;
+  }
+  sink->ranges = true;
+  sink->implied = true;
+  sink->long_columns = long_columns;
+  sink->tightened = out;
+  sink->lists = lists;
+  return true;
+}
+
+void DeviceLp::BoundImpliedPanel(const double* lbs, const double* ubs, int k,
+                                 const double* row_lb, const double* row_ub, double* new_lbs,
+                                 double* new_ubs) {
+  RowPanelSink sink;
+  if (!BoundImpliedBegin(k, row_lb, row_ub, false, nullptr, &sink)) {
+    // Without rows or columns to walk, every column keeps its bounds.
+    const size_t all = size_t(std::max(k, 0)) * size_t(n_total_ - m_);
+    if (all > 0) {
+      std::copy(lbs, lbs + all, new_lbs);
+      std::copy(ubs, ubs + all, new_ubs);
+    }
+    return;
+  }
+  DeviceOp("bound implied panel");
+  sink.sums = new_lbs;
+  sink.max_activity = new_ubs;
+  RowPanels(lbs, ubs, k, sink);
+  panel_->last_bound_implied.bytes_up += 16 * int64_t(k) * (n_total_ - m_);
+  DeviceOp("bound implied panel done");
+}
+
+void DeviceLp::BoundImpliedPanelFrom(const double* base_lb, const double* base_ub, int k,
+                                     const int64_t* starts, const int32_t* cols,
+                                     const double* ov_lbs, const double* ov_ubs,
+                                     const double* row_lb, const double* row_ub, double* new_lbs,
+                                     double* new_ubs) {
+  RowPanelSink sink;
+  if (!BoundImpliedBegin(k, row_lb, row_ub, false, nullptr, &sink)) return;
+  DeviceOp("bound implied panel from");
+  sink.sums = new_lbs;
+  sink.max_activity = new_ubs;
+  sink.from_base = true;
+  panel_->last_bound_implied.bytes_up +=
+      RowPanelsFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, sink);
+  DeviceOp("bound implied panel from done");
+}
+
+void DeviceLp::BoundTightenedPanel(const double* lbs, const double* ubs, int k,
+                                   const double* row_lb, const double* row_ub, double tolerance,
+                                   bool lists, TightenedColumns* out) {
+  RowPanelSink sink;
+  if (!BoundImpliedBegin(k, row_lb, row_ub, lists, out, &sink)) return;
+  DeviceOp("bound tightened panel");
+  sink.tolerance = tolerance;
+  RowPanels(lbs, ubs, k, sink);
+  panel_->last_bound_implied.bytes_up += 16 * int64_t(k) * (n_total_ - m_);
+  DeviceOp("bound tightened panel done");
+}
+
+void DeviceLp::BoundTightenedPanelFrom(const double* base_lb, const double* base_ub, int k,
+                                       const int64_t* starts, const int32_t* cols,
+                                       const double* ov_lbs, const double* ov_ubs,
+                                       const double* row_lb, const double* row_ub,
+                                       double tolerance, bool lists, TightenedColumns* out) {
+  RowPanelSink sink;
+  if (!BoundImpliedBegin(k, row_lb, row_ub, lists, out, &sink)) return;
+  DeviceOp("bound tightened panel from");
+  sink.tolerance = tolerance;
+  sink.from_base = true;
+  panel_->last_bound_implied.bytes_up +=
+      RowPanelsFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, sink);
+  DeviceOp("bound tightened panel from done");
 }
 
 }  // namespace milp

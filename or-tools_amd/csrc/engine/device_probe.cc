@@ -543,6 +543,113 @@ int LastBoundRanges(mi_devop* h, mi_devop_row_violations* out) {
   });
 }
 
+void CheckRowBounds(const mi_devop* h, const char* name, const double* row_lb,
+                    const double* row_ub, double tolerance) {
+  bool ok = row_lb != nullptr && row_ub != nullptr && tolerance >= 0.0 && !std::isinf(tolerance);
+  for (int r = 0; ok && r < h->csc.num_rows(); ++r) {
+    ok = row_lb[r] == row_lb[r] && row_ub[r] == row_ub[r];
+  }
+  if (!ok) throw milp::DeviceError(std::string(name) + ": bad bounds or tolerance");
+}
+
+int BoundImpliedPanel(mi_devop* h, const double* lbs, const double* ubs, int k,
+                      const double* row_lb, const double* row_ub, double* new_lbs,
+                      double* new_ubs) {
+  return Guard(h, [&] {
+    CheckRowBounds(h, "bound_implied_panel", row_lb, row_ub, 0.0);
+    h->dev.BoundImpliedPanel(lbs, ubs, k, row_lb, row_ub, new_lbs, new_ubs);
+  });
+}
+
+int BoundImpliedPanelFrom(mi_devop* h, const double* base_lb, const double* base_ub, int k,
+                          const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                          const double* ov_ubs, const double* row_lb, const double* row_ub,
+                          double* new_lbs, double* new_ubs) {
+  return Guard(h, [&] {
+    CheckRowBounds(h, "bound_implied_panel_from", row_lb, row_ub, 0.0);
+    CheckBoundOverrides(h, "bound_implied_panel_from", k, starts, cols, ov_lbs, ov_ubs);
+    h->dev.BoundImpliedPanelFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, row_lb,
+                                 row_ub, new_lbs, new_ubs);
+  });
+}
+
+// The two filtered entries: run(lists, &result), then the outputs, unless the
+// lists need more than `capacity` entries.
+template <typename Run>
+int TightenedCall(mi_devop* h, const char* name, int k, const double* row_lb,
+                  const double* row_ub, double tolerance, int64_t* col_starts, int32_t* cols,
+                  double* new_lbs, double* new_ubs, int64_t capacity,
+                  mi_devop_point_violations* summaries, Run run) {
+  bool too_large = false;
+  const int rc = Guard(h, [&] {
+    CheckRowBounds(h, name, row_lb, row_ub, tolerance);
+    if (col_starts == nullptr && summaries == nullptr) {
+      throw milp::DeviceError(std::string(name) + ": no outputs");
+    }
+    milp::DeviceLp::TightenedColumns result;
+    run(col_starts != nullptr, &result);
+    if (col_starts != nullptr) {
+      const int64_t kept = result.col_starts.back();
+      if (kept > capacity) {
+        too_large = true;
+        throw milp::DeviceError(std::string(name) + ": " + std::to_string(kept) +
+                                " entries, capacity " + std::to_string(capacity));
+      }
+      std::memcpy(col_starts, result.col_starts.data(),
+                  result.col_starts.size() * sizeof(int64_t));
+      if (kept > 0) {
+        std::memcpy(cols, result.cols.data(), size_t(kept) * sizeof(int32_t));
+        std::memcpy(new_lbs, result.new_lbs.data(), size_t(kept) * sizeof(double));
+        std::memcpy(new_ubs, result.new_ubs.data(), size_t(kept) * sizeof(double));
+      }
+    }
+    if (summaries != nullptr && k > 0) {
+      std::memcpy(summaries, result.summaries.data(), size_t(k) * sizeof(*summaries));
+    }
+  });
+  return too_large ? int{MI_DEVOP_CAPACITY} : rc;
+}
+
+int BoundTightenedPanel(mi_devop* h, const double* lbs, const double* ubs, int k,
+                        const double* row_lb, const double* row_ub, double tolerance,
+                        int64_t* col_starts, int32_t* cols, double* new_lbs, double* new_ubs,
+                        int64_t capacity, mi_devop_point_violations* summaries) {
+  return TightenedCall(h, "bound_tightened_panel", k, row_lb, row_ub, tolerance, col_starts, cols,
+                       new_lbs, new_ubs, capacity, summaries,
+                       [&](bool lists, milp::DeviceLp::TightenedColumns* out) {
+                         h->dev.BoundTightenedPanel(lbs, ubs, k, row_lb, row_ub, tolerance, lists,
+                                                    out);
+                       });
+}
+
+int BoundTightenedPanelFrom(mi_devop* h, const double* base_lb, const double* base_ub, int k,
+                            const int64_t* starts, const int32_t* cols_in, const double* ov_lbs,
+                            const double* ov_ubs, const double* row_lb, const double* row_ub,
+                            double tolerance, int64_t* col_starts, int32_t* cols, double* new_lbs,
+                            double* new_ubs, int64_t capacity,
+                            mi_devop_point_violations* summaries) {
+  return TightenedCall(
+      h, "bound_tightened_panel_from", k, row_lb, row_ub, tolerance, col_starts, cols, new_lbs,
+      new_ubs, capacity, summaries, [&](bool lists, milp::DeviceLp::TightenedColumns* out) {
+        CheckBoundOverrides(h, "bound_tightened_panel_from", k, starts, cols_in, ov_lbs, ov_ubs);
+        h->dev.BoundTightenedPanelFrom(base_lb, base_ub, k, starts, cols_in, ov_lbs, ov_ubs,
+                                       row_lb, row_ub, tolerance, lists, out);
+      });
+}
+
+int LastBoundImplied(mi_devop* h, mi_devop_bound_implied* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastBoundImplied p = h->dev.last_bound_implied();
+    out->panels = p.panels;
+    out->width = p.width;
+    out->columns = p.columns;
+    out->lists = p.lists ? 1 : 0;
+    out->kept = p.kept;
+    out->bytes_up = p.bytes_up;
+    out->bytes_down = p.bytes_down;
+  });
+}
+
 static_assert(sizeof(mi_devop_point_violations) == sizeof(mi_lp_point_violations) &&
                   offsetof(mi_devop_point_violations, worst_row) ==
                       offsetof(mi_lp_point_violations, worst_row),
@@ -586,4 +693,7 @@ extern "C" const mi_devop_api mi_devop_table = {
     BoundRangesPanel, BoundRangesPanelFrom,
     BoundInfeasiblePanel, BoundInfeasiblePanelFrom,
     LastBoundRanges,
+    BoundImpliedPanel, BoundImpliedPanelFrom,
+    BoundTightenedPanel, BoundTightenedPanelFrom,
+    LastBoundImplied,
 };

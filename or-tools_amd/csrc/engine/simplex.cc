@@ -5724,6 +5724,10 @@ struct mi_lp {
   // that built them (rows and, in `activities`, the amounts).
   milp::DeviceLp::RowViolations infeasible_rows;
   bool infeasible_rows_stored = false;
+  // Likewise the lists of the last mi_lp_bound_tightened_columns(_from) call
+  // that built them: a fourth store.
+  milp::DeviceLp::TightenedColumns tightened_columns;
+  bool tightened_columns_stored = false;
   milp::GlopParameters params;
   milp::LinearProgram lp;
   int device = 0;
@@ -6064,6 +6068,7 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t*
   h->sparse_rows_stored = false;  // mi_lp_get_sparse_rows: rows of the LP before
   h->violated_rows_stored = false;  // mi_lp_get_violated_rows: likewise
   h->infeasible_rows_stored = false;  // mi_lp_get_infeasible_rows: likewise
+  h->tightened_columns_stored = false;  // mi_lp_get_tightened_columns: likewise
   if ((n > 0 && (clb == nullptr || cub == nullptr || obj == nullptr)) ||
       (m > 0 && (rlb == nullptr || rub == nullptr))) {
     return MI_LP_ERROR_NULL;
@@ -6637,6 +6642,129 @@ int mi_lp_get_infeasible_rows(const mi_lp* h, int32_t* rows, double* amounts) {
   }
   return MI_LP_OK;
 }
+
+}  // extern "C"
+
+namespace {
+// mi_lp_bound_tightened_columns(_from): run(lists, &result) computes; then
+// the outputs are written and, when lists were built, the result becomes the
+// stored one. Nothing is written or stored unless run returns MI_LP_OK.
+template <typename Run>
+int TightenedCall(mi_lp* h, int32_t k, int64_t* col_starts, mi_lp_point_violations* summaries,
+                  Run run) {
+  return PanelCall(h, [&]() -> int {
+    milp::DeviceLp::TightenedColumns result;
+    const int bad = run(col_starts != nullptr, &result);
+    if (bad != MI_LP_OK) return bad;
+    if (summaries != nullptr) std::copy(result.summaries.begin(), result.summaries.end(), summaries);
+    if (col_starts != nullptr) {
+      std::copy(result.col_starts.begin(), result.col_starts.end(), col_starts);
+      result.summaries.clear();
+      h->tightened_columns = std::move(result);
+      h->tightened_columns_stored = true;
+    }
+    return MI_LP_OK;
+  });
+}
+}  // namespace
+
+extern "C" {
+
+int mi_lp_bound_implied_bounds(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                               const double* row_lb, const double* row_ub, double* new_lbs,
+                               double* new_ubs) {
+  if (h == nullptr || lbs == nullptr || ubs == nullptr || new_lbs == nullptr ||
+      new_ubs == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, 0.0);
+  if (bad != MI_LP_OK) return bad;
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&] {
+    h->simplex.device().BoundImpliedPanel(lbs, ubs, k, row_lb, row_ub, new_lbs, new_ubs);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_bound_implied_bounds_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                    int32_t k, const int64_t* starts, const int32_t* cols,
+                                    const double* ov_lbs, const double* ov_ubs,
+                                    const double* row_lb, const double* row_ub, double* new_lbs,
+                                    double* new_ubs) {
+  if (h == nullptr || base_lb == nullptr || base_ub == nullptr || starts == nullptr ||
+      new_lbs == nullptr || new_ubs == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, 0.0);
+  if (bad != MI_LP_OK) return bad;
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&]() -> int {
+    const int bad_overrides = CheckBoundOverrides(h, k, starts, cols, ov_lbs, ov_ubs);
+    if (bad_overrides != MI_LP_OK) return bad_overrides;
+    h->simplex.device().BoundImpliedPanelFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs,
+                                              row_lb, row_ub, new_lbs, new_ubs);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_bound_tightened_columns(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                                  const double* row_lb, const double* row_ub, double tolerance,
+                                  int64_t* col_starts, mi_lp_point_violations* summaries) {
+  if (h == nullptr || lbs == nullptr || ubs == nullptr ||
+      (col_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  return TightenedCall(h, k, col_starts, summaries,
+                       [&](bool lists, milp::DeviceLp::TightenedColumns* out) {
+                         h->simplex.device().BoundTightenedPanel(lbs, ubs, k, row_lb, row_ub,
+                                                                 tolerance, lists, out);
+                         return int{MI_LP_OK};
+                       });
+}
+
+int mi_lp_bound_tightened_columns_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                       int32_t k, const int64_t* starts, const int32_t* cols,
+                                       const double* ov_lbs, const double* ov_ubs,
+                                       const double* row_lb, const double* row_ub,
+                                       double tolerance, int64_t* col_starts,
+                                       mi_lp_point_violations* summaries) {
+  if (h == nullptr || base_lb == nullptr || base_ub == nullptr || starts == nullptr ||
+      (col_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  return TightenedCall(
+      h, k, col_starts, summaries, [&](bool lists, milp::DeviceLp::TightenedColumns* out) -> int {
+        const int bad_overrides = CheckBoundOverrides(h, k, starts, cols, ov_lbs, ov_ubs);
+        if (bad_overrides != MI_LP_OK) return bad_overrides;
+        h->simplex.device().BoundTightenedPanelFrom(base_lb, base_ub, k, starts, cols, ov_lbs,
+                                                    ov_ubs, row_lb, row_ub, tolerance, lists,
+                                                    out);
+        return MI_LP_OK;
+      });
+}
+
+int mi_lp_get_tightened_columns(const mi_lp* h, int32_t* cols, double* new_lbs,
+                                double* new_ubs) {
+  if (h == nullptr || cols == nullptr || new_lbs == nullptr || new_ubs == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->tightened_columns_stored) return MI_LP_ERROR_STATE;
+  const size_t kept = h->tightened_columns.cols.size();
+  if (kept > 0) {
+    std::memcpy(cols, h->tightened_columns.cols.data(), kept * sizeof(int32_t));
+    std::memcpy(new_lbs, h->tightened_columns.new_lbs.data(), kept * sizeof(double));
+    std::memcpy(new_ubs, h->tightened_columns.new_ubs.data(), kept * sizeof(double));
+  }
+  return MI_LP_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals) {
   if (h == nullptr || cols == nullptr || vals == nullptr) return MI_LP_ERROR_NULL;

@@ -144,7 +144,14 @@ struct PointViolations {  // mi_lp_point_violations of include/mi_lp.h
 // below) under the second rule: `in` then holds g per (row, child), row r
 // proves child v infeasible when g > tolerance, and its amount is g (> 0,
 // never NaN). row_lb / row_ub are not read under that rule.
-enum PanelRowRule { kRowRuleOutsideBounds = 0, kRowRuleAboveTolerance = 1 };
+//
+// The third rule serves the implied column bounds (implied_bounds_panel
+// below): `in` holds one key per (column, child), num_rows is the number of
+// columns, a key >= 0 is kept and a key > 0 is a crossing column with that
+// amount. A kept column that does not cross enters the worst-merge without an
+// index, so a summary has count > 0 and worst_row == -1 when no column
+// crosses. row_lb / row_ub / tolerance are not read under that rule.
+enum PanelRowRule { kRowRuleOutsideBounds = 0, kRowRuleAboveTolerance = 1, kRowRuleKeptKey = 2 };
 struct RowViolationArgs {
   const double* in;      // interleaved row sums (or g), num_rows x K
   int num_rows;
@@ -188,6 +195,54 @@ struct ActivityRangeArgs {
   const double* row_lb;  // num_rows each, or both nullptr
   const double* row_ub;
   double* out;
+};
+
+// Implied column bounds of a panel of K bound sets (panel_kernels.hip,
+// implied_bounds_panel; include/mi_lp.h mi_lp_bound_implied_bounds has the
+// rule): the column direction over activity_ranges_panel's dense result.
+// `ranges` is that kernel's `out` (row_lb == nullptr): lo, hi and the packed
+// counts, three row-interleaved blocks of num_rows x K. lower / upper are the
+// column-interleaved own bounds that kernel read. The CSC covers the
+// num_cols structural columns (rows < num_rows). Results are
+// column-interleaved, new_lower[col * K + v] and new_upper[col * K + v],
+// written for v < kp.
+//   keys != nullptr  also one key per (column, child), keys[col * K + v]:
+//                    -1.0 for a column that is not kept, the crossing amount
+//                    nl - nu (> tolerance >= 0) for a crossing column, else
+//                    0.0. The kRowRuleKeptKey passes (below) filter them.
+//   base_lb != nullptr  the override form: a column whose own bounds differ in
+//                    bits from base_lb[col] / base_ub[col] is kept too.
+struct ImpliedBoundsArgs {
+  const int64_t* starts;  // CSC, num_cols + 1
+  const int32_t* rows;
+  const double* vals;
+  const double* ranges;
+  const double* row_lb;  // num_rows each
+  const double* row_ub;
+  const double* lower;
+  const double* upper;
+  int num_rows;
+  int num_cols;
+  int kp;  // children in use (<= K)
+  double tolerance;
+  const double* base_lb;  // num_cols each, or both nullptr
+  const double* base_ub;
+  double* new_lower;
+  double* new_upper;
+  double* keys;
+};
+// new_lower / new_upper at the kept columns of the kRowRuleKeptKey write pass:
+// child v's kept columns are cols[sum of totals[0 .. v) ...], and
+// out_lower / out_upper receive the two bounds at the same positions.
+struct ImpliedGatherArgs {
+  const int64_t* totals;  // kp
+  const int32_t* cols;
+  const double* new_lower;  // column-interleaved, num_cols x K
+  const double* new_upper;
+  int num_cols;
+  int kp;
+  double* out_lower;
+  double* out_upper;
 };
 
 // Where an update-row kernel that emits the list itself puts it: the
@@ -590,6 +645,14 @@ hipError_t row_violations_panel(int width, int rule, const milp_kernels::RowViol
 // over the rows of [A | I] (panel_kernels.hip activity_ranges_panel_kernel).
 hipError_t activity_ranges_panel(int width, const milp_kernels::ActivityRangeArgs& args,
                                  hipStream_t s);
+// After activity_ranges_panel (dense mode) on the same stream: the implied
+// bounds of the structural columns for the same panel. long_columns: one
+// workgroup per column, else 256 / width columns per workgroup
+// (panel_kernels.hip implied_bounds_panel_kernel).
+hipError_t implied_bounds_panel(int width, bool long_columns,
+                                const milp_kernels::ImpliedBoundsArgs& args, hipStream_t s);
+// After row_violations_panel under kRowRuleKeptKey with lists.
+hipError_t implied_gather(int width, const milp_kernels::ImpliedGatherArgs& args, hipStream_t s);
 hipError_t dense_pack(const int64_t* starts, const double* vals, const int32_t* dense_cols,
                       int nd, int m, double* body, double* tail, hipStream_t s);
 hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hipStream_t s);

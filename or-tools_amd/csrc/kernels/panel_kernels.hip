@@ -25,7 +25,10 @@
 // the rows outside their bounds and one summary per point) comes after it.
 // Last, the activity ranges of the rows under a panel of K bound sets
 // (activity_ranges_panel_kernel), whose screening form goes through the same
-// count, fold and write passes under a second rule.
+// count, fold and write passes under a second rule, and the implied column
+// bounds over those ranges (implied_bounds_panel_short_kernel /
+// implied_bounds_panel_long_kernel: the column direction again, over the row
+// direction's result), whose filtered form goes through them under a third.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -546,6 +549,27 @@ struct RowRule<kRowRuleAboveTolerance> {
     return x > a.tolerance;
   }
 };
+// The keys of implied_bounds_panel_kernel: kept when >= 0 (never NaN), and
+// the key is the amount. An amount of 0.0 is a kept column that does not
+// cross: worst_index() keeps it out of the merge's indices, since 0.0 at a
+// real index would replace the (0.0, kNoWorstRow) start.
+template <>
+struct RowRule<kRowRuleKeptKey> {
+  static __device__ __forceinline__ bool keep(const RowViolationArgs&, double x, int,
+                                              double* amount) {
+    *amount = x;
+    return x >= 0.0;
+  }
+  static __device__ __forceinline__ bool keep(const RowViolationArgs&, double x, int) {
+    return x >= 0.0;
+  }
+};
+// The index a kept element enters the worst-merge with.
+template <int RULE>
+__device__ __forceinline__ int worst_index(double amount, int index) {
+  if constexpr (RULE == kRowRuleKeptKey) return amount > 0.0 ? index : kNoWorstRow;
+  return index;
+}
 
 // panel_count_kernel's tile and thread layout: thread t reads elements t,
 // t + 256, ... of the tile's 256 * K contiguous doubles and meets one point
@@ -578,7 +602,7 @@ __global__ __launch_bounds__(kPanelTileColumns) void violations_count_kernel(
         double row_amount;
         if (RowRule<RULE>::keep(a, x, row0 + rl, &row_amount)) {
           ++c;
-          worst_merge(&amount, &worst_row, row_amount, row0 + rl);
+          worst_merge(&amount, &worst_row, row_amount, worst_index<RULE>(row_amount, row0 + rl));
         }
       }
     }
@@ -617,6 +641,9 @@ __global__ __launch_bounds__(kPanelTileColumns) void violations_count_kernel(
 
 // Workgroup v folds point v's tile partials into its summary: the integer
 // sum of the counts, the largest amount and the lowest row attaining it.
+// kIndexOptional (kRowRuleKeptKey): kept elements may all be without an index,
+// and the summary's worst_row is then -1 beside a count > 0.
+template <bool kIndexOptional>
 __global__ __launch_bounds__(kPanelOffsetsStep) void violations_fold_kernel(RowViolationArgs a) {
   constexpr int kWaves = kPanelOffsetsStep / kWave;
   __shared__ long long wave_count[kWaves];
@@ -653,8 +680,9 @@ __global__ __launch_bounds__(kPanelOffsetsStep) void violations_fold_kernel(RowV
     }
     PointViolations s;
     s.count = c;
-    s.worst = c > 0 ? amount : 0.0;
-    s.worst_row = c > 0 ? worst_row : -1;
+    const bool any = kIndexOptional ? worst_row != kNoWorstRow : c > 0;
+    s.worst = any ? amount : 0.0;
+    s.worst_row = any ? worst_row : -1;
     s.reserved = 0;
     a.summaries[v] = s;
   }
@@ -768,6 +796,215 @@ __global__ __launch_bounds__(kRowPanelThreads) void activity_ranges_panel_kernel
   }
 }
 
+// ---------------------------------------------------------------------------
+// Implied column bounds under a panel of K bound sets: one round of bound
+// propagation over activity_ranges_panel_kernel's dense result
+// (include/mi_lp.h mi_lp_bound_implied_bounds has the rule; the argument
+// block says what is read and stored). The column direction: per entry (r, a)
+// of a structural column, child v gathers lo[r * K + v], hi[r * K + v] and the
+// packed counts at r * K + v (three contiguous reads of K words over the K
+// lanes of a column) and the two row bounds, forms at most one candidate for
+// each of its two bounds and keeps the largest lower and the smallest upper
+// candidate. Every candidate is rounded on its own (a product, a difference,
+// a difference, a quotient, + 0.0) and the result is a max and a min of them,
+// so it has the same bits in any order: the two shapes below differ only in
+// who walks which entries.
+//
+// One side of an entry: the row bound rb, the range sum s with cnt infinite
+// terms, and the bound b that this column fed into s. No candidate unless rb
+// is finite and either no term is infinite (the column's own term leaves the
+// sum) or the column's own is the only one. + 0.0 turns a -0.0 quotient into
+// +0.0, so that equal candidates have equal bits.
+__device__ __forceinline__ void implied_candidate(double rb, double s, int cnt, double b, double a,
+                                                  double* q, bool* ok) {
+  const bool b_is_inf = fabs(b) == __builtin_inf();
+  const double res = cnt == 0 ? s - a * b : s;
+  const double quotient = (rb - res) / a;
+  *ok = fabs(rb) < __builtin_inf() && (cnt == 0 || (cnt == 1 && b_is_inf)) &&
+        fabs(quotient) < __builtin_inf();  // false for a NaN quotient
+  *q = quotient + 0.0;
+}
+
+// The sign of `a` is one value for the K lanes of a column but not for a
+// wave: selects, as in activity_range_term. The lo side (against row_ub)
+// tightens the upper bound of a column with a > 0 and the lower bound
+// otherwise; the hi side the other one. A zero or NaN entry gives nothing. A
+// NaN own bound fails every comparison and stays.
+__device__ __forceinline__ void implied_term(double a, double l, double u, double lo, double hi,
+                                             unsigned long long counts, double rlb, double rub,
+                                             double* nl, double* nu) {
+  const bool live = a != 0.0 && a == a;
+  const bool up = a > 0.0;
+  const double bl = up ? l : u;
+  const double bh = up ? u : l;
+  double q_lo, q_hi;
+  bool ok_lo, ok_hi;
+  implied_candidate(rub, lo, static_cast<int>(counts & 0xffffffffull), bl, a, &q_lo, &ok_lo);
+  implied_candidate(rlb, hi, static_cast<int>(counts >> 32), bh, a, &q_hi, &ok_hi);
+  const double for_upper = up ? q_lo : q_hi;
+  const double for_lower = up ? q_hi : q_lo;
+  const bool upper_ok = live && (up ? ok_lo : ok_hi);
+  const bool lower_ok = live && (up ? ok_hi : ok_lo);
+  *nu = (upper_ok && for_upper < *nu) ? for_upper : *nu;
+  *nl = (lower_ok && for_lower > *nl) ? for_lower : *nl;
+}
+
+// The results of (col, v) and, in list mode, its key (ImpliedBoundsArgs).
+// Every difference is one rounded operation; inf - inf is NaN and fails its
+// comparison.
+__device__ __forceinline__ void implied_store(const ImpliedBoundsArgs& a, int col, int64_t at,
+                                              double l, double u, double nl, double nu) {
+  a.new_lower[at] = nl;
+  a.new_upper[at] = nu;
+  if (a.keys == nullptr) return;
+  const bool moved = (nl - l > a.tolerance) || (u - nu > a.tolerance);
+  const double cross = nl - nu;
+  const bool crossing = cross > a.tolerance;
+  bool changed = false;
+  if (a.base_lb != nullptr) {
+    changed = __double_as_longlong(l) != __double_as_longlong(a.base_lb[col]) ||
+              __double_as_longlong(u) != __double_as_longlong(a.base_ub[col]);
+  }
+  a.keys[at] = crossing ? cross : ((moved || changed) ? 0.0 : -1.0);
+}
+
+// Short columns: thread t owns (column t / K of the workgroup's 256 / K,
+// child t % K), as the row kernels own (row, child). The column is walked
+// with the gathers of kRowPanelUnroll entries issued ahead of the compares;
+// no LDS, no barrier and no cross-lane step. The padding children read the
+// unwritten part of `ranges` and store nothing.
+template <int K>
+__global__ __launch_bounds__(kRowPanelThreads) void implied_bounds_panel_short_kernel(
+    ImpliedBoundsArgs a) {
+  static_assert(kRowPanelThreads % K == 0, "whole columns per workgroup");
+  constexpr int kCols = kRowPanelThreads / K;
+  const int v = threadIdx.x % K;
+  const int col = blockIdx.x * kCols + threadIdx.x / K;
+  if (col >= a.num_cols) return;
+  const int64_t s = a.starts[col];
+  const int64_t e = a.starts[col + 1];
+  const int64_t block = static_cast<int64_t>(a.num_rows) * K;
+  const double* __restrict__ lo_all = a.ranges + v;
+  const double* __restrict__ hi_all = a.ranges + block + v;
+  const unsigned long long* __restrict__ counts_all =
+      reinterpret_cast<const unsigned long long*>(a.ranges) + 2 * block + v;
+  const int64_t at = static_cast<int64_t>(col) * K + v;
+  const double l = a.lower[at];
+  const double u = a.upper[at];
+  double nl = l;
+  double nu = u;
+  int64_t i = s;
+  for (; i + kRowPanelUnroll <= e; i += kRowPanelUnroll) {
+    int row[kRowPanelUnroll];
+    double val[kRowPanelUnroll];
+    double lo[kRowPanelUnroll];
+    double hi[kRowPanelUnroll];
+    unsigned long long counts[kRowPanelUnroll];
+    double rlb[kRowPanelUnroll];
+    double rub[kRowPanelUnroll];
+#pragma unroll
+    for (int j = 0; j < kRowPanelUnroll; ++j) {
+      row[j] = a.rows[i + j];
+      val[j] = a.vals[i + j];
+    }
+#pragma unroll
+    for (int j = 0; j < kRowPanelUnroll; ++j) {
+      const int64_t r = static_cast<int64_t>(row[j]) * K;
+      lo[j] = lo_all[r];
+      hi[j] = hi_all[r];
+      counts[j] = counts_all[r];
+      rlb[j] = a.row_lb[row[j]];
+      rub[j] = a.row_ub[row[j]];
+    }
+#pragma unroll
+    for (int j = 0; j < kRowPanelUnroll; ++j) {
+      implied_term(val[j], l, u, lo[j], hi[j], counts[j], rlb[j], rub[j], &nl, &nu);
+    }
+  }
+  for (; i < e; ++i) {
+    const int row = a.rows[i];
+    const int64_t r = static_cast<int64_t>(row) * K;
+    implied_term(a.vals[i], l, u, lo_all[r], hi_all[r], counts_all[r], a.row_lb[row],
+                 a.row_ub[row], &nl, &nu);
+  }
+  if (v >= a.kp) return;
+  implied_store(a, col, at, l, u, nl, nu);
+}
+
+// Long columns: one workgroup per column. Thread t is child t % K and slice
+// t / K of the 256 / K slices and walks the entries slice, slice + 256 / K,
+// ...; every slice starts from the own bounds. The partials of a child fold
+// by shuffles over the lanes l, l + K, l + 2K, ... of a wave and then over the
+// four waves through LDS: a max and a min, exact in any order.
+template <int K>
+__global__ __launch_bounds__(kRowPanelThreads) void implied_bounds_panel_long_kernel(
+    ImpliedBoundsArgs a) {
+  static_assert(kRowPanelThreads % K == 0 && kWave % K == 0, "a thread owns one child");
+  constexpr int kSlices = kRowPanelThreads / K;
+  constexpr int kWaves = kRowPanelThreads / kWave;
+  __shared__ double wave_lower[kWaves][K];
+  __shared__ double wave_upper[kWaves][K];
+  const int t = threadIdx.x;
+  const int v = t % K;
+  const int slice = t / K;
+  const int col = blockIdx.x;  // < num_cols: the grid is exactly num_cols workgroups
+  const int64_t s = a.starts[col];
+  const int64_t e = a.starts[col + 1];
+  const int64_t block = static_cast<int64_t>(a.num_rows) * K;
+  const double* __restrict__ lo_all = a.ranges + v;
+  const double* __restrict__ hi_all = a.ranges + block + v;
+  const unsigned long long* __restrict__ counts_all =
+      reinterpret_cast<const unsigned long long*>(a.ranges) + 2 * block + v;
+  const int64_t at = static_cast<int64_t>(col) * K + v;
+  const double l = a.lower[at];
+  const double u = a.upper[at];
+  double nl = l;
+  double nu = u;
+  for (int64_t i = s + slice; i < e; i += kSlices) {
+    const int row = a.rows[i];
+    const int64_t r = static_cast<int64_t>(row) * K;
+    implied_term(a.vals[i], l, u, lo_all[r], hi_all[r], counts_all[r], a.row_lb[row],
+                 a.row_ub[row], &nl, &nu);
+  }
+#pragma unroll
+  for (int off = K; off < kWave; off <<= 1) {
+    const double other_lower = __shfl_xor(nl, off, kWave);
+    const double other_upper = __shfl_xor(nu, off, kWave);
+    nl = other_lower > nl ? other_lower : nl;
+    nu = other_upper < nu ? other_upper : nu;
+  }
+  const int lane = t & (kWave - 1);
+  const int wave = t / kWave;
+  if (lane < K) {  // lane == v
+    wave_lower[wave][lane] = nl;
+    wave_upper[wave][lane] = nu;
+  }
+  __syncthreads();
+  if (t >= a.kp) return;  // t == v below
+  nl = wave_lower[0][t];
+  nu = wave_upper[0][t];
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) {
+    nl = wave_lower[w][t] > nl ? wave_lower[w][t] : nl;
+    nu = wave_upper[w][t] < nu ? wave_upper[w][t] : nu;
+  }
+  implied_store(a, col, at, l, u, nl, nu);
+}
+
+// The two bounds at the kept columns of the kRowRuleKeptKey write pass
+// (ImpliedGatherArgs): workgroup (x, v) takes entries x * 256 ... of child v.
+template <int K>
+__global__ __launch_bounds__(256) void implied_gather_kernel(ImpliedGatherArgs a) {
+  const int v = blockIdx.y;  // < kp
+  int64_t start = 0;
+  for (int j = 0; j < v; ++j) start += a.totals[j];
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= a.totals[v]) return;
+  const int64_t from = static_cast<int64_t>(a.cols[start + i]) * K + v;
+  a.out_lower[start + i] = a.new_lower[from];
+  a.out_upper[start + i] = a.new_upper[from];
+}
+
 }  // namespace milp_kernels
 
 namespace milp_launch {
@@ -851,13 +1088,38 @@ hipError_t activity_ranges_panel(int width, const ActivityRangeArgs& args, hipSt
   });
 }
 
+hipError_t implied_bounds_panel(int width, bool long_columns, const ImpliedBoundsArgs& args,
+                                hipStream_t s) {
+  if (args.num_cols <= 0 || args.kp <= 0) return hipSuccess;
+  if ((args.base_lb == nullptr) != (args.base_ub == nullptr)) return hipErrorInvalidValue;
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    if (long_columns) {
+      implied_bounds_panel_long_kernel<K><<<args.num_cols, kRowPanelThreads, 0, s>>>(args);
+    } else {
+      const int blocks = panel_div_up(args.num_cols, kRowPanelThreads / K);
+      implied_bounds_panel_short_kernel<K><<<blocks, kRowPanelThreads, 0, s>>>(args);
+    }
+  });
+}
+
+hipError_t implied_gather(int width, const ImpliedGatherArgs& args, hipStream_t s) {
+  if (args.num_cols <= 0 || args.kp <= 0) return hipSuccess;
+  const dim3 grid(panel_div_up(args.num_cols, 256), args.kp);
+  return for_panel_width(width, [&](auto w) {
+    implied_gather_kernel<decltype(w)::value><<<grid, 256, 0, s>>>(args);
+  });
+}
+
 // launch(std::integral_constant<int, RULE>) for a PanelRowRule.
 template <typename Launch>
 static void for_row_rule(int rule, Launch launch) {
   if (rule == kRowRuleOutsideBounds) {
     launch(std::integral_constant<int, kRowRuleOutsideBounds>());
-  } else {
+  } else if (rule == kRowRuleAboveTolerance) {
     launch(std::integral_constant<int, kRowRuleAboveTolerance>());
+  } else {
+    launch(std::integral_constant<int, kRowRuleKeptKey>());
   }
 }
 
@@ -865,7 +1127,8 @@ hipError_t row_violations_panel(int width, int rule, const RowViolationArgs& arg
                                 hipStream_t s) {
   if (args.num_rows <= 0 || args.kp <= 0) return hipSuccess;
   if (args.tiles != panel_div_up(args.num_rows, kPanelTileColumns)) return hipErrorInvalidValue;
-  if (rule != kRowRuleOutsideBounds && rule != kRowRuleAboveTolerance) {
+  if (rule != kRowRuleOutsideBounds && rule != kRowRuleAboveTolerance &&
+      rule != kRowRuleKeptKey) {
     return hipErrorInvalidValue;
   }
   return for_panel_width(width, [&](auto w) {
@@ -884,7 +1147,11 @@ hipError_t row_violations_panel(int width, int rule, const RowViolationArgs& arg
       panel_offsets_kernel<<<1, kPanelOffsetsStep, 0, s>>>(o);
     }
     if (args.summaries != nullptr) {
-      violations_fold_kernel<<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
+      if (rule == kRowRuleKeptKey) {
+        violations_fold_kernel<true><<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
+      } else {
+        violations_fold_kernel<false><<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
+      }
     }
     if (args.rows != nullptr) {
       for_row_rule(rule, [&](auto r) {

@@ -388,6 +388,20 @@ def branch_overrides(trail, x, cols):
     return base_lb, base_ub, overrides
 
 
+def tightened_overrides(result):
+    """LpHandle.tightened_columns(_from)'s result (col_starts, cols, new_lbs,
+    new_ubs, summaries) as overrides[j] = (cols, new_lbs, new_ubs), one per
+    set: what every *_from call of LpHandle takes. From tightened_columns_from
+    a set's list is its complete override list relative to the same base, so
+    the overrides feed a second round, infeasible_rows_from, or (materialised)
+    batch_solve_bounds."""
+    col_starts, cols, new_lbs, new_ubs = result[:4]
+    if col_starts is None:
+        raise ValueError("the result has no lists (lists=False)")
+    return [(cols[s:e], new_lbs[s:e], new_ubs[s:e])
+            for s, e in zip(col_starts[:-1], col_starts[1:])]
+
+
 def fold_node(trail, x, cols, results):
     """Folds batched branch results (MiLpResult per branch LP, in branch_lps
     order) with BranchOnVar's decisions, column by column. Returns a summary:

@@ -139,6 +139,13 @@ def lib():
     L.mi_lp_bound_infeasible_rows_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 6 + [
         ctypes.c_double, vp, vp]
     L.mi_lp_get_infeasible_rows.argtypes = [vp, vp, vp]
+    L.mi_lp_bound_implied_bounds.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp]
+    L.mi_lp_bound_implied_bounds_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 8
+    L.mi_lp_bound_tightened_columns.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp,
+                                                ctypes.c_double, vp, vp]
+    L.mi_lp_bound_tightened_columns_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 6 + [
+        ctypes.c_double, vp, vp]
+    L.mi_lp_get_tightened_columns.argtypes = [vp, vp, vp, vp]
     L.mi_lp_solver_params_default.argtypes = [ctypes.POINTER(abi.MiLpSolverParams)]
     L.mi_lp_scale.argtypes = [ctypes.POINTER(abi.MiLpSolverParams), ctypes.c_int32,
                               ctypes.c_int32] + [vp] * 14
@@ -805,6 +812,73 @@ class LpHandle:
         args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
         return self._infeasible("bound_infeasible_rows_from", k, lists, args, row_lb, row_ub,
                                 tolerance)
+
+    def _implied(self, name, k, args, row_lb, row_ub):
+        lb, ub = self._row_bounds(row_lb, "row_lb"), self._row_bounds(row_ub, "row_ub")
+        n = self.lp.n
+        new_lbs = np.zeros((max(k, 1), max(n, 1)), np.float64)
+        new_ubs = np.zeros((max(k, 1), max(n, 1)), np.float64)
+        self._call(name, *args, None if lb is None else _p(lb), None if ub is None else _p(ub),
+                   _p(new_lbs), _p(new_ubs))
+        return new_lbs[:k, :n], new_ubs[:k, :n]
+
+    def implied_bounds(self, lbs, ubs, row_lb=None, row_ub=None):
+        """One round of bound propagation on the GPU: the implied bounds of
+        every structural column under each of k bound sets (lbs, ubs: (k, n)),
+        from the activity ranges of bound_activity_ranges and the row bounds
+        (None: the loaded ones). Returns (new_lbs, new_ubs), each (k, n), with
+        new_lbs >= lbs and new_ubs <= ubs. The rule (include/mi_lp.h
+        mi_lp_bound_implied_bounds) is the textbook one in doubles and is not
+        outward-rounded."""
+        lbs, ubs, k = self._bound_sets(lbs, ubs)
+        return self._implied("bound_implied_bounds", k, (_p(lbs), _p(ubs), k), row_lb, row_ub)
+
+    def implied_bounds_from(self, base_lb, base_ub, overrides, row_lb=None, row_ub=None):
+        """implied_bounds of the sets of bound_activity_ranges_from(base_lb,
+        base_ub, overrides), built on the GPU."""
+        args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
+        return self._implied("bound_implied_bounds_from", k, args, row_lb, row_ub)
+
+    def _tightened(self, name, k, lists, args, row_lb, row_ub, tolerance):
+        lb, ub = self._row_bounds(row_lb, "row_lb"), self._row_bounds(row_ub, "row_ub")
+        starts = np.zeros(max(k, 1) + 1, np.int64) if lists else None
+        summaries = np.zeros(max(k, 1), POINT_VIOLATIONS)
+        self._call(name, *args, None if lb is None else _p(lb), None if ub is None else _p(ub),
+                   ctypes.c_double(tolerance), None if starts is None else _p(starts),
+                   _p(summaries))
+        if not lists:
+            return None, None, None, None, summaries[:k]
+        kept = int(starts[k])
+        cols = np.zeros(max(1, kept), np.int32)
+        new_lbs = np.zeros(max(1, kept), np.float64)
+        new_ubs = np.zeros(max(1, kept), np.float64)
+        self._call("get_tightened_columns", _p(cols), _p(new_lbs), _p(new_ubs))
+        return starts[:k + 1], cols[:kept], new_lbs[:kept], new_ubs[:kept], summaries[:k]
+
+    def tightened_columns(self, lbs, ubs, row_lb=None, row_ub=None, tolerance=0.0, lists=True):
+        """implied_bounds filtered on the GPU: per set the columns whose bound
+        moved by more than tolerance or whose implied bounds cross by more
+        than it. Returns (col_starts[k+1] int64, cols int32, new_lbs, new_ubs,
+        summaries): set j's kept columns, ascending, are
+        cols[col_starts[j]:col_starts[j+1]] with their implied bounds beside
+        them; summaries (POINT_VIOLATIONS) hold the number of kept columns,
+        the largest crossing amount and the lowest column attaining it
+        (worst_row, -1 without a crossing column). A set is proven infeasible
+        by propagation iff worst_row >= 0. With lists=False only the summaries
+        come down and the first four are None."""
+        lbs, ubs, k = self._bound_sets(lbs, ubs)
+        return self._tightened("bound_tightened_columns", k, lists, (_p(lbs), _p(ubs), k), row_lb,
+                               row_ub, tolerance)
+
+    def tightened_columns_from(self, base_lb, base_ub, overrides, row_lb=None, row_ub=None,
+                               tolerance=0.0, lists=True):
+        """tightened_columns of the sets base + overrides; a column whose own
+        bounds differ in bits from the base is kept too, so a set's list is
+        its complete override list relative to the base
+        (cpsat.tightened_overrides turns the result into overrides)."""
+        args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
+        return self._tightened("bound_tightened_columns_from", k, lists, args, row_lb, row_ub,
+                               tolerance)
 
 
 def batch_solve(handles, num_threads=4, progress=None, progress_s=15.0):
