@@ -592,9 +592,10 @@ int mi_lp_get_infeasible_rows(const mi_lp* h, int32_t* rows, double* amounts);
  * neither sees nor disturbs the other three. With MILP_SHARDS the calls stay
  * on the unsplit handle. No solve uses these calls and they change no state a
  * later solve reads.
- * Out of scope: integer rounding of the results (a caller rounds the short
- * list); more than one round per call; a packed or double2 layout of the
- * three range blocks; a per-column choice between the two kernel shapes. */
+ * Integer rounding of the results and more than one round per call are
+ * mi_lp_bound_propagate's (below), not these calls'.
+ * Out of scope: a packed or double2 layout of the three range blocks; a
+ * per-column choice between the two kernel shapes. */
 int mi_lp_bound_implied_bounds(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
                                const double* row_lb, const double* row_ub, double* new_lbs,
                                double* new_ubs);
@@ -613,6 +614,122 @@ int mi_lp_bound_tightened_columns_from(mi_lp* h, const double* base_lb, const do
                                        double tolerance, int64_t* col_starts,
                                        mi_lp_point_violations* summaries);
 int mi_lp_get_tightened_columns(const mi_lp* h, int32_t* cols, double* new_lbs, double* new_ubs);
+
+/* Node propagation: those rounds repeated on the GPU until nothing moves, a
+ * column crosses or max_rounds is reached, with integer columns rounded; the
+ * bound sets, the ranges and the implied bounds stay on the GPU between
+ * rounds and 24 bytes per set come down per round. Inputs beside the sets:
+ * row_lb / row_ub as above; is_integer, n bytes, non-zero marks an integer
+ * column, NULL means none; tolerance >= 0, finite; integrality_tolerance in
+ * [0, 0.5), finite; max_rounds >= 1. Per set j, with own bounds (l, u):
+ *   status = MI_LP_PROPAGATE_ROUND_LIMIT; rounds = 0; moves = 0
+ *   worst = 0.0; worst_col = -1
+ *   for round = 1 .. max_rounds:
+ *     (nl, nu) = the result of mi_lp_bound_implied_bounds on (l, u), bit for bit
+ *     for every column c < n:
+ *       if is_integer[c]: nl[c] = ceil(nl[c] - integrality_tolerance) + 0.0
+ *                         nu[c] = floor(nu[c] + integrality_tolerance) + 0.0
+ *       moved = (nl[c] - l[c] > tolerance) || (u[c] - nu[c] > tolerance)
+ *       if moved: (l'[c], u'[c]) = (nl[c], nu[c])      BOTH sides
+ *       else:     (l'[c], u'[c]) = (l[c], u[c])
+ *       cross = l'[c] - u'[c];  crossing = cross > tolerance
+ *     (l, u) = (l', u'); rounds = round; moves += number of moved columns
+ *     if some column crosses: status = MI_LP_PROPAGATE_INFEASIBLE
+ *                             worst = the largest cross
+ *                             worst_col = the lowest column attaining it; stop
+ *     if no column moved:     status = MI_LP_PROPAGATE_FIXPOINT; stop
+ * The difference and the sum inside ceil / floor are one rounded operation
+ * each, ceil and floor are exact and + 0.0 turns -0.0 into +0.0; an infinity
+ * stays and a NaN stays. inf - inf and every difference with a NaN are NaN
+ * and fail their comparison: a NaN own bound stays NaN and never moves. A set
+ * whose own bounds already cross stops INFEASIBLE in round 1, and an
+ * INFEASIBLE set keeps the bounds of the round that found the crossing. A
+ * moved column takes both new bounds, as a kept column of
+ * mi_lp_bound_tightened_columns_from does when its list is fed back; rounding
+ * can therefore put the side that did not move below (above) the own bound by
+ * less than one. The rounds are Jacobi rounds: every column of a round reads
+ * the bounds of the round's start, so with the one-round rule's order
+ * independence every bit of the result is independent of the reduction
+ * order, the kernel shape, the panel width and of which other sets share the
+ * call. Like the one-round rule it is NOT outward-rounded: the tolerances are
+ * filters, not safety margins.
+ * moves is exact: it counts moved columns only. A column that crosses without
+ * having moved exists only in round 1 (its own bounds cross); it is kept out
+ * of moves by a second count over move-only keys, made for the sets that stop
+ * INFEASIBLE in round 1 and for no other.
+ * With is_integer == NULL and tolerance == 0, a set that is not INFEASIBLE
+ * before round R has after R rounds exactly the bits of R calls of
+ * mi_lp_bound_tightened_columns_from, each list fed back as that set's
+ * overrides. (With a tolerance > 0 the fed-back list also carries nl and nu of
+ * the columns it keeps only because they differ from the base, which this
+ * rule leaves at their own bounds while they move by no more than the
+ * tolerance.)
+ *   mi_lp_bound_propagate       dense sets in; the final (l, u) into new_lbs /
+ *                               new_ubs, k x n each, set-major, and one
+ *                               mi_lp_propagation per set (summaries may be
+ *                               NULL). kept = the number of columns whose
+ *                               final l or u differs in bits from the input.
+ *   mi_lp_bound_propagate_from  the same for the sets base + overrides, built
+ *                               on the GPU; bit for bit the dense form on the
+ *                               materialised sets, kept included.
+ *   mi_lp_bound_propagated_columns_from
+ *                               keeps per set the columns whose final l or u
+ *                               differs IN BITS from base_lb / base_ub, or
+ *                               that cross (l - u > tolerance), ascending,
+ *                               each with its final l and u; kept = the
+ *                               length of the set's list. The list is the
+ *                               set's complete override list relative to the
+ *                               base: it feeds mi_lp_bound_infeasible_rows_from,
+ *                               another propagate call or (materialised)
+ *                               mi_lp_batch_solve_bounds. Stores the lists and
+ *                               writes col_starts (k + 1) and summaries;
+ *                               col_starts == NULL means summaries only, and a
+ *                               previously stored list stays.
+ *   mi_lp_get_propagated_columns  copies the stored columns and bounds out,
+ *                               col_starts[k] of each.
+ * NULL handling, k = 0, the state before a solve, MILP_SHARDS (the calls stay
+ * on the unsplit handle) and every error code are those of
+ * mi_lp_bound_tightened_columns(_from); in addition max_rounds < 1 and an
+ * integrality_tolerance that is negative, NaN or >= 0.5 are
+ * MI_LP_ERROR_INVALID_PROBLEM. Nothing is written on an error. The stored
+ * lists are a fifth store of the handle; it neither sees nor disturbs the
+ * other four. No solve uses these calls and they change no state a later
+ * solve reads.
+ * Out of scope: fusing the apply step into the implied-bound kernels; a
+ * device-side round loop without the per-round 24 k byte download; a row-side
+ * infeasibility screen per round (a caller runs
+ * mi_lp_bound_infeasible_rows_from on the result); outward rounding; a
+ * per-column choice between the two implied-bound kernel shapes; lists in the
+ * dense-input form; using the result inside any solve. */
+#define MI_LP_PROPAGATE_ROUND_LIMIT 0
+#define MI_LP_PROPAGATE_FIXPOINT 1
+#define MI_LP_PROPAGATE_INFEASIBLE 2
+typedef struct mi_lp_propagation {
+  int32_t status;    /* MI_LP_PROPAGATE_* */
+  int32_t rounds;    /* rounds this set took part in */
+  int64_t moves;     /* moved columns, summed over the rounds */
+  double worst;      /* INFEASIBLE: the largest cross; else 0.0 */
+  int32_t worst_col; /* INFEASIBLE: the lowest column attaining it; else -1 */
+  int32_t kept;      /* see the calls above */
+} mi_lp_propagation;
+int mi_lp_bound_propagate(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                          const uint8_t* is_integer, const double* row_lb, const double* row_ub,
+                          double tolerance, double integrality_tolerance, int32_t max_rounds,
+                          double* new_lbs, double* new_ubs, mi_lp_propagation* summaries);
+int mi_lp_bound_propagate_from(mi_lp* h, const double* base_lb, const double* base_ub, int32_t k,
+                               const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                               const double* ov_ubs, const uint8_t* is_integer,
+                               const double* row_lb, const double* row_ub, double tolerance,
+                               double integrality_tolerance, int32_t max_rounds, double* new_lbs,
+                               double* new_ubs, mi_lp_propagation* summaries);
+int mi_lp_bound_propagated_columns_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                        int32_t k, const int64_t* starts, const int32_t* cols,
+                                        const double* ov_lbs, const double* ov_ubs,
+                                        const uint8_t* is_integer, const double* row_lb,
+                                        const double* row_ub, double tolerance,
+                                        double integrality_tolerance, int32_t max_rounds,
+                                        int64_t* col_starts, mi_lp_propagation* summaries);
+int mi_lp_get_propagated_columns(const mi_lp* h, int32_t* cols, double* new_lbs, double* new_ubs);
 
 /* interrupt may be NULL; a non-zero value stops the solve like a time limit
  * (glop_interface.cc:138-140). */

@@ -138,6 +138,37 @@ typedef struct mi_devop_bound_implied {
   int64_t bytes_up;   /* host-to-device bytes of the call: the sets and 16 m of row bounds */
   int64_t bytes_down; /* device-to-host bytes of the call */
 } mi_devop_bound_implied;
+/* mi_lp_propagation of include/mi_lp.h, restated so that this header stands
+ * alone. */
+typedef struct mi_devop_propagation {
+  int32_t status; /* 0 round limit, 1 fixpoint, 2 infeasible */
+  int32_t rounds;
+  int64_t moves;
+  double worst;
+  int32_t worst_col; /* -1 unless infeasible */
+  int32_t kept;
+} mi_devop_propagation;
+/* Parameters of the propagate entries. is_integer: n bytes, or NULL. */
+typedef struct mi_devop_propagate_params {
+  const uint8_t* is_integer;
+  double tolerance;             /* finite, >= 0 (checked by the entries) */
+  double integrality_tolerance; /* in [0, 0.5) */
+  int32_t max_rounds;           /* >= 1 */
+  int32_t reserved;
+} mi_devop_propagate_params;
+/* DeviceLp::LastBoundPropagate: the last bound_propagate_panel(_from) or
+ * bound_propagated_columns_from. */
+typedef struct mi_devop_bound_propagate {
+  int32_t panels;     /* panels of up to 16 bound sets */
+  int32_t width;      /* padded width of the last panel: 1, 4 or 16 */
+  int32_t columns;    /* implied-bound kernel shape of the last panel */
+  int32_t lists;      /* lists were built (col_starts given) */
+  int64_t rounds;     /* rounds launched, summed over the panels */
+  int64_t kept;       /* entries of all lists */
+  int64_t bytes_up;   /* the sets, 16 m of row bounds and n of is_integer */
+  int64_t bytes_down; /* 24 per set and round (twice in a round 1 that finds a crossing),
+                         then the results */
+} mi_devop_bound_propagate;
 
 typedef struct mi_devop_api {
   /* A (m x n) in CSC; the m slack columns are appended. NULL on failure. */
@@ -305,6 +336,33 @@ typedef struct mi_devop_api {
                                     double* new_lbs, double* new_ubs, int64_t capacity,
                                     mi_devop_point_violations* summaries);
   int (*last_bound_implied)(mi_devop* h, mi_devop_bound_implied* out);
+  /* Appended after last_bound_implied. DeviceLp::BoundPropagatePanel (the
+   * rule: include/mi_lp.h mi_lp_bound_propagate). lbs / ubs and new_lbs /
+   * new_ubs: k x n; row_lb / row_ub as bound_implied_panel; params checked
+   * here; summaries: k, not NULL. */
+  int (*bound_propagate_panel)(mi_devop* h, const double* lbs, const double* ubs, int k,
+                               const mi_devop_propagate_params* params, const double* row_lb,
+                               const double* row_ub, double* new_lbs, double* new_ubs,
+                               mi_devop_propagation* summaries);
+  /* The sets and their checks as bound_ranges_panel_from. */
+  int (*bound_propagate_panel_from)(mi_devop* h, const double* base_lb, const double* base_ub,
+                                    int k, const int64_t* starts, const int32_t* cols,
+                                    const double* ov_lbs, const double* ov_ubs,
+                                    const mi_devop_propagate_params* params,
+                                    const double* row_lb, const double* row_ub, double* new_lbs,
+                                    double* new_ubs, mi_devop_propagation* summaries);
+  /* DeviceLp::BoundPropagatedColumnsFrom in one call. col_starts, cols,
+   * new_lbs, new_ubs and capacity as bound_tightened_panel_from,
+   * MI_DEVOP_CAPACITY included; summaries: k, or NULL. */
+  int (*bound_propagated_columns_from)(mi_devop* h, const double* base_lb, const double* base_ub,
+                                       int k, const int64_t* starts, const int32_t* cols_in,
+                                       const double* ov_lbs, const double* ov_ubs,
+                                       const mi_devop_propagate_params* params,
+                                       const double* row_lb, const double* row_ub,
+                                       int64_t* col_starts, int32_t* cols, double* new_lbs,
+                                       double* new_ubs, int64_t capacity,
+                                       mi_devop_propagation* summaries);
+  int (*last_bound_propagate)(mi_devop* h, mi_devop_bound_propagate* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

@@ -21,6 +21,7 @@ struct TriSolveArgs;
 struct ScanState;
 struct ListOut;
 struct TightenState;
+struct ImpliedBoundsArgs;
 }
 namespace sdual {
 struct Mailbox;
@@ -388,6 +389,68 @@ class DeviceLp : public DeviceSolver {
   };
   LastBoundImplied last_bound_implied() const;
 
+  // --- bound propagation of k bound sets to a fixpoint (include/mi_lp.h
+  // mi_lp_bound_propagate has the rule) -----
+  // The sets travel as for BoundImpliedPanel(From) and stay in the workspace.
+  // Per panel and round: the activity ranges and the implied bounds, both
+  // kernels as they are; propagate_apply_panel_kernel rounds the integer
+  // columns, moves the own bounds in place and writes one key per (column,
+  // set); the count and fold passes of the row violations turn the keys into
+  // one 24-byte summary per set, which comes down; the host updates status,
+  // rounds and moves and the mask of stopped sets. A panel's loop ends when
+  // all its sets have stopped or at max_rounds. A set that stops INFEASIBLE
+  // in round 1 may hold columns that cross without a move (own bounds that
+  // cross): for those sets alone the round's moves come from a second count
+  // and fold over move-only keys. is_integer: n bytes, host, or null.
+  struct PropagateParams {
+    const uint8_t* is_integer = nullptr;
+    double tolerance = 0.0;
+    double integrality_tolerance = 0.0;
+    int max_rounds = 1;
+  };
+  // Dense results: the final bounds, k x n each, vector-major; summaries: k.
+  // kept = the columns of the set whose final bounds differ in bits from its
+  // input (counted on the host: both arrays are there).
+  void BoundPropagatePanel(const double* lbs, const double* ubs, int k,
+                           const PropagateParams& params, const double* row_lb,
+                           const double* row_ub, double* new_lbs, double* new_ubs,
+                           mi_lp_propagation* summaries);
+  void BoundPropagatePanelFrom(const double* base_lb, const double* base_ub, int k,
+                               const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                               const double* ov_ubs, const PropagateParams& params,
+                               const double* row_lb, const double* row_ub, double* new_lbs,
+                               double* new_ubs, mi_lp_propagation* summaries);
+  // The filtered form: propagate_changed_keys_kernel keys the final bounds
+  // against the base (differ in bits, or cross), and the count, offsets, fold
+  // and write passes and the gather of the tightened columns bring the kept
+  // (column, l, u) entries down. kept = the length of the set's list.
+  struct PropagatedColumns {
+    TightenedColumns lists;  // its summaries: the filter's own (count = kept)
+    std::vector<mi_lp_propagation> summaries;  // k
+  };
+  void BoundPropagatedColumnsFrom(const double* base_lb, const double* base_ub, int k,
+                                  const int64_t* starts, const int32_t* cols,
+                                  const double* ov_lbs, const double* ov_ubs,
+                                  const PropagateParams& params, const double* row_lb,
+                                  const double* row_ub, bool lists, PropagatedColumns* out);
+  // The last of these three calls (test record). rounds: the rounds launched,
+  // summed over the panels (per panel the largest `rounds` of its sets).
+  // bytes_up: the sets and row bounds as LastBoundImplied, plus n for
+  // is_integer. bytes_down: 24 kp per round (twice in a round 1 that finds a
+  // crossing), then 16 k n for the dense results, 20 kept + 32 k with lists,
+  // 24 k for summaries only.
+  struct LastBoundPropagate {
+    int panels = 0;
+    int width = 0;             // of the last panel
+    int columns = kPanelNone;  // implied-bound kernel shape of the last panel
+    bool lists = false;
+    int64_t rounds = 0;
+    int64_t kept = 0;  // entries of all lists
+    int64_t bytes_up = 0;
+    int64_t bytes_down = 0;
+  };
+  LastBoundPropagate last_bound_propagate() const;
+
   // --- dual device mode: device-resident reduced costs ------------------
   // (see simplex.cc RevisedSimplex::DualDeviceMode). colbits: one byte per
   // column (kernel_args.h kCol*), bound_diff: upper - lower per column.
@@ -633,7 +696,8 @@ class DeviceLp : public DeviceSolver {
     int sparse_cols = 0;
   };
   PanelPlan PanelKernelChoice() const;
-  void PanelReserve(int width, int kp, bool ranges = false, bool implied = false);
+  void PanelReserve(int width, int kp, bool ranges = false, bool implied = false,
+                    bool propagate = false);
   void PanelUploadVectors(const double* y, int first, int kp, int width);
   void PanelLaunchDots(const PanelPlan& plan, int kp, int width);
   void PanelRecord(const PanelPlan& plan, int width, LastPanel* record) const;
@@ -660,6 +724,14 @@ class DeviceLp : public DeviceSolver {
     bool long_columns = false;
     TightenedColumns* tightened = nullptr;
     bool from_base = false;
+    // Bound propagation (with `ranges` and `implied`): RowPanelPropagate runs
+    // the panel's rounds. propagation: k summaries. Dense form: final_lbs /
+    // final_ubs take the final bounds (k x n, host); filtered form:
+    // `tightened` with `lists`.
+    const PropagateParams* propagate = nullptr;
+    mi_lp_propagation* propagation = nullptr;
+    double* final_lbs = nullptr;
+    double* final_ubs = nullptr;
   };
   // upper: the second array of a ranges call (k x n beside x's k x n), else
   // null (x is k x N).
@@ -684,6 +756,37 @@ class DeviceLp : public DeviceSolver {
   // launch (k <= 0, no rows or no structural columns).
   bool BoundImpliedBegin(int k, const double* row_lb, const double* row_ub, bool lists,
                          TightenedColumns* out, RowPanelSink* sink);
+  // What BoundImpliedBegin and BoundPropagateBegin share: the row bounds up
+  // and the column shape (MILP_IMPLIED_COLUMNS) into `sink`; false when there
+  // is nothing to launch. Touches no record.
+  bool PanelImpliedSetup(int k, const double* row_lb, const double* row_ub, RowPanelSink* sink);
+  // The launches the one-round calls and the round loop share: the activity
+  // ranges of the panel in `cols` / `cols_upper` into `rows` (screening: g
+  // alone, against row_lb / row_ub), and the argument block of the implied
+  // bounds over them (results into `implied`; no keys, no base).
+  void PanelLaunchRanges(int kp, int width, bool screening);
+  milp_kernels::ImpliedBoundsArgs PanelImpliedArgs(int kp, int width) const;
+  // The filter over one key per (column, set) of the panel: count, offsets,
+  // fold and write, then (lists) the gather of lower / upper at the kept
+  // columns; down come the kp summaries into out->summaries and, with lists,
+  // the kp totals and the kept entries, appended set-major. Adds to *kept and
+  // *bytes_down. what: the call, for an error's text.
+  void PanelKeptColumns(int first, int kp, int width, const double* keys, const double* lower,
+                        const double* upper, bool lists, PanelTimer* timer, TightenedColumns* out,
+                        int64_t* kept, int64_t* bytes_down, const char* what);
+  // The sets of one panel are in `cols` / `cols_upper`: the rounds, then the
+  // dense or the filtered form of the final bounds.
+  void RowPanelPropagate(int first, int kp, int width, PanelTimer* timer,
+                         const RowPanelSink& sink);
+  // BoundImpliedBegin for the propagate calls: their record, is_integer up.
+  bool BoundPropagateBegin(int k, const PropagateParams& params, const double* row_lb,
+                           const double* row_ub, bool lists, PropagatedColumns* out,
+                           mi_lp_propagation* summaries, RowPanelSink* sink);
+  // The rule on the host for a matrix without rows or columns (nothing to
+  // launch), and BoundPropagatedColumnsFrom's keep rule beside it. No test
+  // loads such a matrix: this path is untested.
+  static void PropagateWithoutRows(const PropagateParams& params, int n, double* l, double* u,
+                                   mi_lp_propagation* summary);
   bool is_shard_ = false;
   std::vector<std::unique_ptr<DeviceLp>> shards_;  // null: a block owned by another process
   ExchangeFn exchange_fn_ = nullptr;

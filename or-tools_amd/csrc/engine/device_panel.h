@@ -1,8 +1,9 @@
 // The workspace of DeviceLp's panel calls (device_panel.hip): the buffers of
 // ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel, RowSumsPanelFrom,
 // RowViolationsPanel(From), BoundRangesPanel(From),
-// BoundInfeasiblePanel(From), BoundImpliedPanel(From) and
-// BoundTightenedPanel(From), their timing events and their test records.
+// BoundInfeasiblePanel(From), BoundImpliedPanel(From),
+// BoundTightenedPanel(From), BoundPropagatePanel(From) and
+// BoundPropagatedColumnsFrom, their timing events and their test records.
 // Included by the HIP translation units only; device_lp.h holds the workspace
 // behind a pointer.
 #ifndef MILP_DEVICE_PANEL_H_
@@ -110,7 +111,20 @@ struct PanelWorkspace {
   // form's packed lower bounds, upper bounds and keys (kept_cols beside them).
   // PanelReserve(ranges, implied) sizes them for that. row_lb / row_ub and,
   // in the override form, base / base_upper are read as uploaded.
+  //
+  // The bound propagation (BoundPropagatePanel(From),
+  // BoundPropagatedColumnsFrom) repeats that per round on the same buffers:
+  // `rows` takes the round's ranges, `implied`'s first two blocks the round's
+  // implied bounds, and propagate_apply_panel_kernel moves the own bounds in
+  // `cols` / `cols_upper` IN PLACE, writes the round's keys into the third
+  // block and, in round 1, move-only keys into a fourth
+  // (PanelReserve(ranges, implied, propagate) sizes `implied` at four blocks).
+  // `is_integer` (below) is read as uploaded. After the rounds `flat` takes
+  // the final bounds on their way down, two blocks of kp n, or the packed
+  // kept bounds and keys as for the tightened columns, whose keys
+  // propagate_changed_keys_kernel writes into the third block of `implied`.
   DeviceBuffer<double> implied;
+  DeviceBuffer<uint8_t> is_integer;  // the propagation only: n, uploaded once per call
   PinnedBuffer<double> y_staging;  // column dots: the host interleave of y, max(1, m width)
 
   // ColumnDotsPanelSparse and the row violations: tiles of 256 columns
@@ -149,6 +163,7 @@ struct PanelWorkspace {
   DeviceLp::LastRowViolations last_row_violations;
   DeviceLp::LastBoundRanges last_bound_ranges;
   DeviceLp::LastBoundImplied last_bound_implied;
+  DeviceLp::LastBoundPropagate last_bound_propagate;
 };
 
 }  // namespace milp

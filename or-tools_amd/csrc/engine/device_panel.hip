@@ -3,14 +3,18 @@
 // RowSumsPanelFrom), their violated rows (RowViolationsPanel,
 // RowViolationsPanelFrom) and the activity ranges of bound sets
 // (BoundRangesPanel(From), BoundInfeasiblePanel(From)) with the implied column
-// bounds over them (BoundImpliedPanel(From), BoundTightenedPanel(From)) share
+// bounds over them (BoundImpliedPanel(From), BoundTightenedPanel(From)) and
+// their rounds to a fixpoint (BoundPropagatePanel(From),
+// BoundPropagatedColumnsFrom) share
 // one workspace (device_panel.h), one panel loop and one timing scope. No
 // solve calls them and nothing a solve reads is written.
 #include "device_panel.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../kernels/kernel_args.h"
@@ -53,6 +57,11 @@ class PanelTimer {
     PanelCheck(hipEventElapsedTime(&ms, w_->ev[0], w_->ev[1]), "ev time");
     w_->kernel_ms += ms;
   }
+  // A panel with more than one synchronizing download (the rounds of the
+  // bound propagation): after Downloaded(), the next stretch starts here.
+  void Restart() {
+    if (w_->timing) PanelCheck(hipEventRecord(w_->ev[0], stream_), "ev");
+  }
 
  private:
   PanelWorkspace* w_;
@@ -94,9 +103,9 @@ void DeviceLp::RowPanelGeometry(int rows_per_workgroup[3], int* chunk) {
 // Grows the three shared buffers to one panel of `width` holding `kp`
 // vectors. The stream is idle between panels (each ends with a synchronizing
 // download).
-// ranges, implied: the roles of the activity ranges and of the implied column
-// bounds over them (device_panel.h).
-void DeviceLp::PanelReserve(int width, int kp, bool ranges, bool implied) {
+// ranges, implied, propagate: the roles of the activity ranges, of the implied
+// column bounds over them and of the propagation's rounds (device_panel.h).
+void DeviceLp::PanelReserve(int width, int kp, bool ranges, bool implied, bool propagate) {
   const size_t n = size_t(n_total_ - m_);
   size_t rows = size_t(m_) * width;
   size_t flat = size_t(n_total_) * kp;
@@ -108,7 +117,8 @@ void DeviceLp::PanelReserve(int width, int kp, bool ranges, bool implied) {
   }
   if (implied) {
     flat = std::max(flat, 3 * n * kp);
-    panel_->implied.Reserve(3 * std::max<size_t>(1, n) * width, "panel implied bounds");
+    panel_->implied.Reserve((propagate ? 4 : 3) * std::max<size_t>(1, n) * width,
+                            "panel implied bounds");
   }
   panel_->rows.Reserve(std::max<size_t>(1, rows), "panel rows");
   panel_->cols.Reserve(size_t(n_total_) * width, "panel columns");
@@ -284,28 +294,34 @@ bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const 
   return true;
 }
 
+void DeviceLp::PanelLaunchRanges(int kp, int width, bool screening) {
+  PanelWorkspace& w = *panel_;
+  milp_kernels::ActivityRangeArgs a{};
+  a.t_starts = d_t_starts_;
+  a.t_cols = d_t_cols_;
+  a.t_vals = d_t_vals_;
+  a.lower = w.cols.get();
+  a.upper = w.cols_upper.get();
+  a.num_rows = m_;
+  a.num_structural = n_total_ - m_;
+  a.kp = kp;
+  if (screening) {  // g alone
+    a.row_lb = w.row_lb.get();
+    a.row_ub = w.row_ub.get();
+  }
+  a.out = w.rows.get();
+  Check(milp_launch::activity_ranges_panel(width, a, S(stream_)), "activity ranges panel");
+}
+
 // The interleaved points of one panel are in `cols`: the sums into `rows`;
 // then the dense form (vector-major into `flat`, down to sink.sums, and the
 // record) or the violations form.
 void DeviceLp::RowPanelSums(int first, int kp, int width, PanelTimer* timer,
                             const RowPanelSink& sink) {
   PanelWorkspace& w = *panel_;
+  if (sink.propagate != nullptr) return RowPanelPropagate(first, kp, width, timer, sink);
   if (sink.ranges) {
-    milp_kernels::ActivityRangeArgs a{};
-    a.t_starts = d_t_starts_;
-    a.t_cols = d_t_cols_;
-    a.t_vals = d_t_vals_;
-    a.lower = w.cols.get();
-    a.upper = w.cols_upper.get();
-    a.num_rows = m_;
-    a.num_structural = n_total_ - m_;
-    a.kp = kp;
-    if (sink.violations != nullptr) {  // screening: g alone
-      a.row_lb = w.row_lb.get();
-      a.row_ub = w.row_ub.get();
-    }
-    a.out = w.rows.get();
-    Check(milp_launch::activity_ranges_panel(width, a, S(stream_)), "activity ranges panel");
+    PanelLaunchRanges(kp, width, sink.violations != nullptr);
   } else {
     milp_kernels::RowPanelArgs a{};
     a.t_starts = d_t_starts_;
@@ -362,7 +378,7 @@ void DeviceLp::RowPanels(const double* x, const double* upper, int k, const RowP
   PanelWorkspace& w = *panel_;
   const int ncols = sink.ranges ? n_total_ - m_ : n_total_;
   ForEachPanel(k, [&](int first, int kp, int width) {
-    PanelReserve(width, kp, sink.ranges, sink.implied);
+    PanelReserve(width, kp, sink.ranges, sink.implied, sink.propagate != nullptr);
     const size_t up = size_t(kp) * ncols;
     Upload(w.flat.get(), x + size_t(first) * ncols, up * sizeof(double));
     if (sink.ranges) Upload(w.flat.get() + up, upper + size_t(first) * ncols, up * sizeof(double));
@@ -416,7 +432,7 @@ int64_t DeviceLp::RowPanelsFrom(const double* base, const double* base_upper, in
           "row panel overrides");
   };
   ForEachPanel(k, [&](int first, int kp, int width) {
-    PanelReserve(width, kp, sink.ranges, sink.implied);
+    PanelReserve(width, kp, sink.ranges, sink.implied, sink.propagate != nullptr);
     PanelTimer timer(&w, S(stream_));
     build(w.base.get(), w.ov_vals.get(), w.cols.get(), first, kp, width);
     if (sink.ranges) {
@@ -698,25 +714,12 @@ void DeviceLp::RowPanelImplied(int first, int kp, int width, PanelTimer* timer,
   const size_t block = size_t(n) * width;
   const size_t down = size_t(kp) * n;
   TightenedColumns* out = sink.tightened;
-  milp_kernels::ImpliedBoundsArgs a{};
-  a.starts = d_starts_;
-  a.rows = d_rows_;
-  a.vals = d_vals_;
-  a.ranges = w.rows.get();
-  a.row_lb = w.row_lb.get();
-  a.row_ub = w.row_ub.get();
-  a.lower = w.cols.get();
-  a.upper = w.cols_upper.get();
-  a.num_rows = m_;
-  a.num_cols = n;
-  a.kp = kp;
+  milp_kernels::ImpliedBoundsArgs a = PanelImpliedArgs(kp, width);
   a.tolerance = sink.tolerance;
   if (out != nullptr && sink.from_base) {
     a.base_lb = w.base.get();
     a.base_ub = w.base_upper.get();
   }
-  a.new_lower = w.implied.get();
-  a.new_upper = w.implied.get() + block;
   a.keys = out != nullptr ? w.implied.get() + 2 * block : nullptr;
   Check(milp_launch::implied_bounds_panel(width, sink.long_columns, a, S(stream_)),
         "implied bounds panel");
@@ -738,12 +741,43 @@ void DeviceLp::RowPanelImplied(int first, int kp, int width, PanelTimer* timer,
     record.bytes_down += 16 * int64_t(down);
     return;
   }
+  PanelKeptColumns(first, kp, width, a.keys, a.new_lower, a.new_upper, sink.lists, timer, out,
+                   &record.kept, &record.bytes_down, "tightened columns panel");
+}
+
+milp_kernels::ImpliedBoundsArgs DeviceLp::PanelImpliedArgs(int kp, int width) const {
+  PanelWorkspace& w = *panel_;
+  const int n = n_total_ - m_;
+  milp_kernels::ImpliedBoundsArgs a{};
+  a.starts = d_starts_;
+  a.rows = d_rows_;
+  a.vals = d_vals_;
+  a.ranges = w.rows.get();
+  a.row_lb = w.row_lb.get();
+  a.row_ub = w.row_ub.get();
+  a.lower = w.cols.get();
+  a.upper = w.cols_upper.get();
+  a.num_rows = m_;
+  a.num_cols = n;
+  a.kp = kp;
+  a.new_lower = w.implied.get();
+  a.new_upper = w.implied.get() + size_t(n) * width;
+  return a;
+}
+
+void DeviceLp::PanelKeptColumns(int first, int kp, int width, const double* keys,
+                                const double* lower, const double* upper, bool lists,
+                                PanelTimer* timer, TightenedColumns* out, int64_t* kept_total,
+                                int64_t* bytes_down, const char* what) {
+  PanelWorkspace& w = *panel_;
+  const int n = n_total_ - m_;
+  const size_t down = size_t(kp) * n;
   const int tiles = (n + milp_kernels::kPanelTileColumns - 1) / milp_kernels::kPanelTileColumns;
   w.counts.Reserve(size_t(kp) * tiles, "panel counts");
   w.tile_worst.Reserve(size_t(kp) * tiles, "panel tile worst");
   w.tile_worst_row.Reserve(size_t(kp) * tiles, "panel tile worst row");
   milp_kernels::RowViolationArgs v{};
-  v.in = a.keys;
+  v.in = keys;
   v.num_rows = n;
   v.kp = kp;
   v.tiles = tiles;
@@ -751,7 +785,7 @@ void DeviceLp::RowPanelImplied(int first, int kp, int width, PanelTimer* timer,
   v.tile_worst = w.tile_worst.get();
   v.tile_worst_row = w.tile_worst_row.get();
   const int64_t* totals = nullptr;
-  if (sink.lists) {
+  if (lists) {
     w.kept_cols.Reserve(size_t(n) * kp, "panel kept columns");
     w.offsets.Reserve(size_t(kp) * tiles + milp_kernels::kPanelMaxWidth, "panel offsets");
     totals = w.totals.Reserve(milp_kernels::kPanelMaxWidth, "panel totals");
@@ -764,25 +798,25 @@ void DeviceLp::RowPanelImplied(int first, int kp, int width, PanelTimer* timer,
   const milp_kernels::PointViolations* host_summaries =
       w.summaries_host.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
   Check(milp_launch::row_violations_panel(width, milp_kernels::kRowRuleKeptKey, v, S(stream_)),
-        "tightened columns panel");
-  if (sink.lists) {
+        what);
+  if (lists) {
     milp_kernels::ImpliedGatherArgs g{};
     g.totals = v.totals;
     g.cols = v.rows;
-    g.new_lower = a.new_lower;
-    g.new_upper = a.new_upper;
+    g.new_lower = lower;
+    g.new_upper = upper;
     g.num_cols = n;
     g.kp = kp;
     g.out_lower = w.flat.get();
     g.out_upper = w.flat.get() + down;
-    Check(milp_launch::implied_gather(width, g, S(stream_)), "tightened columns gather");
+    Check(milp_launch::implied_gather(width, g, S(stream_)), what);
   }
   timer->Launched();
   Download(w.summaries_host.get(), v.summaries, size_t(kp) * sizeof(*v.summaries));
   for (int c = 0; c < kp; ++c) {
     const milp_kernels::PointViolations& s = host_summaries[c];
     if (s.count < 0 || s.count > n || s.worst_row < -1 || s.worst_row >= n) {
-      throw DeviceError("tightened columns panel: bad summary");
+      throw DeviceError(std::string(what) + ": bad summary");
     }
     mi_lp_point_violations& d = out->summaries[first + c];
     d.count = s.count;
@@ -790,12 +824,12 @@ void DeviceLp::RowPanelImplied(int first, int kp, int width, PanelTimer* timer,
     d.worst_row = s.worst_row;
     d.reserved = 0;
   }
-  record.bytes_down += int64_t(kp) * 24;
-  if (sink.lists) {
+  *bytes_down += int64_t(kp) * 24;
+  if (lists) {
     Download(w.totals.get(), v.totals, size_t(kp) * sizeof(int64_t));
     int64_t kept = 0;
     for (int c = 0; c < kp; ++c) {
-      if (totals[c] < 0 || totals[c] > n) throw DeviceError("tightened columns panel: bad count");
+      if (totals[c] < 0 || totals[c] > n) throw DeviceError(std::string(what) + ": bad count");
       kept += totals[c];
       out->col_starts[first + c + 1] = out->col_starts[first + c] + totals[c];
     }
@@ -812,8 +846,8 @@ void DeviceLp::RowPanelImplied(int first, int kp, int width, PanelTimer* timer,
             "D2H");
       Download(out->new_lbs.data() + old, w.flat.get(), size_t(kept) * sizeof(double));
     }
-    record.kept += kept;
-    record.bytes_down += int64_t(kp) * 8 + kept * 20;
+    *kept_total += kept;
+    *bytes_down += int64_t(kp) * 8 + kept * 20;
   }
   timer->Downloaded();
 }
@@ -831,13 +865,22 @@ bool DeviceLp::BoundImpliedBegin(int k, const double* row_lb, const double* row_
     out->new_ubs.clear();
     out->summaries.assign(sets, mi_lp_point_violations{0, 0.0, -1, 0});
   }
+  if (!PanelImpliedSetup(k, row_lb, row_ub, sink)) return false;
+  w.last_bound_implied.bytes_up = 16 * int64_t(m_);
+  sink->tightened = out;
+  sink->lists = lists;
+  return true;
+}
+
+bool DeviceLp::PanelImpliedSetup(int k, const double* row_lb, const double* row_ub,
+                                 RowPanelSink* sink) {
+  PanelWorkspace& w = *panel_;
   const int n = n_total_ - m_;
   if (k <= 0 || m_ <= 0 || n <= 0) return false;
   Upload(w.row_lb.Reserve(size_t(m_), "panel row lower bounds"), row_lb,
          size_t(m_) * sizeof(double));
   Upload(w.row_ub.Reserve(size_t(m_), "panel row upper bounds"), row_ub,
          size_t(m_) * sizeof(double));
-  w.last_bound_implied.bytes_up = 16 * int64_t(m_);
   // Long columns when the structural entries per structural column are >= 32.
   // PanelKernelChoice's average leaves the dense block's columns out.
   bool long_columns = double(h_starts_[n]) / n >= 32.0;
@@ -849,8 +892,6 @@ bool DeviceLp::BoundImpliedBegin(int k, const double* row_lb, const double* row_
   sink->ranges = true;
   sink->implied = true;
   sink->long_columns = long_columns;
-  sink->tightened = out;
-  sink->lists = lists;
   return true;
 }
 
@@ -916,6 +957,345 @@ void DeviceLp::BoundTightenedPanelFrom(const double* base_lb, const double* base
   panel_->last_bound_implied.bytes_up +=
       RowPanelsFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, sink);
   DeviceOp("bound tightened panel from done");
+}
+
+DeviceLp::LastBoundPropagate DeviceLp::last_bound_propagate() const {
+  return panel_->last_bound_propagate;
+}
+
+namespace {
+const mi_lp_propagation kPropagationStart = {MI_LP_PROPAGATE_ROUND_LIMIT, 0, 0, 0.0, -1, 0};
+
+bool SameBits(double a, double b) {
+  uint64_t x, y;
+  std::memcpy(&x, &a, sizeof(x));
+  std::memcpy(&y, &b, sizeof(y));
+  return x == y;
+}
+
+// Columns of (l, u) that differ in bits from (from_l, from_u).
+int32_t ChangedColumns(const double* l, const double* u, const double* from_l,
+                       const double* from_u, int n) {
+  int32_t changed = 0;
+  for (int c = 0; c < n; ++c) {
+    if (!SameBits(l[c], from_l[c]) || !SameBits(u[c], from_u[c])) ++changed;
+  }
+  return changed;
+}
+
+// Set j of base + overrides into l / u (n each).
+void MaterialiseSet(const double* base_lb, const double* base_ub, int n, int j,
+                    const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                    const double* ov_ubs, double* l, double* u) {
+  std::copy(base_lb, base_lb + n, l);
+  std::copy(base_ub, base_ub + n, u);
+  for (int64_t i = starts[j]; i < starts[j + 1]; ++i) {
+    l[cols[i]] = ov_lbs[i];
+    u[cols[i]] = ov_ubs[i];
+  }
+}
+}  // namespace
+
+// The sets of one panel are in `cols` / `cols_upper`. Every round ends with a
+// synchronizing download of kp summaries; the timer covers each stretch of
+// launches on its own.
+void DeviceLp::RowPanelPropagate(int first, int kp, int width, PanelTimer* timer,
+                                 const RowPanelSink& sink) {
+  PanelWorkspace& w = *panel_;
+  LastBoundPropagate& record = w.last_bound_propagate;
+  const PropagateParams& params = *sink.propagate;
+  const int n = n_total_ - m_;
+  const size_t block = size_t(n) * width;
+  const size_t down = size_t(kp) * n;
+  const int tiles = (n + milp_kernels::kPanelTileColumns - 1) / milp_kernels::kPanelTileColumns;
+  w.counts.Reserve(size_t(kp) * tiles, "panel counts");
+  w.tile_worst.Reserve(size_t(kp) * tiles, "panel tile worst");
+  w.tile_worst_row.Reserve(size_t(kp) * tiles, "panel tile worst row");
+  const milp_kernels::ImpliedBoundsArgs implied = PanelImpliedArgs(kp, width);
+  milp_kernels::PropagateApplyArgs apply{};
+  apply.new_lower = implied.new_lower;
+  apply.new_upper = implied.new_upper;
+  apply.lower = w.cols.get();
+  apply.upper = w.cols_upper.get();
+  apply.is_integer = params.is_integer != nullptr ? w.is_integer.get() : nullptr;
+  apply.num_cols = n;
+  apply.kp = kp;
+  apply.tolerance = params.tolerance;
+  apply.integrality_tolerance = params.integrality_tolerance;
+  apply.keys = w.implied.get() + 2 * block;
+  double* const moved_keys = w.implied.get() + 3 * block;
+  milp_kernels::RowViolationArgs v{};  // summaries only: count and fold
+  v.num_rows = n;
+  v.kp = kp;
+  v.tiles = tiles;
+  v.counts = w.counts.get();
+  v.tile_worst = w.tile_worst.get();
+  v.tile_worst_row = w.tile_worst_row.get();
+  v.summaries = w.summaries.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
+  const milp_kernels::PointViolations* host_summaries =
+      w.summaries_host.Reserve(milp_kernels::kPanelMaxWidth, "panel summaries");
+  // The kp summaries of `keys`, down.
+  auto summarise = [&](const double* keys) {
+    v.in = keys;
+    Check(milp_launch::row_violations_panel(width, milp_kernels::kRowRuleKeptKey, v, S(stream_)),
+          "bound propagate summaries");
+    timer->Launched();
+    Download(w.summaries_host.get(), v.summaries, size_t(kp) * sizeof(*v.summaries));
+    timer->Downloaded();
+    for (int c = 0; c < kp; ++c) {
+      const milp_kernels::PointViolations& s = host_summaries[c];
+      if (s.count < 0 || s.count > n || s.worst_row < -1 || s.worst_row >= n) {
+        throw DeviceError("bound propagate panel: bad summary");
+      }
+    }
+    record.bytes_down += int64_t(kp) * 24;
+    timer->Restart();
+  };
+  mi_lp_propagation* out = sink.propagation + first;
+  const uint32_t all = (uint32_t{1} << kp) - 1;  // kp <= kPanelMaxWidth = 16
+  uint32_t stopped = 0;
+  for (int round = 1; round <= params.max_rounds && stopped != all; ++round) {
+    PanelLaunchRanges(kp, width, false);
+    Check(milp_launch::implied_bounds_panel(width, sink.long_columns, implied, S(stream_)),
+          "implied bounds panel");
+    apply.frozen = stopped;
+    apply.moved_keys = round == 1 ? moved_keys : nullptr;
+    Check(milp_launch::propagate_apply(width, apply, S(stream_)), "bound propagate apply");
+    summarise(apply.keys);
+    record.rounds += 1;
+    uint32_t recount = 0;  // stopped INFEASIBLE in round 1: own bounds may cross without a move
+    for (int c = 0; c < kp; ++c) {
+      if ((stopped >> c) & 1u) continue;
+      const milp_kernels::PointViolations& s = host_summaries[c];
+      out[c].rounds = round;
+      if (s.worst_row >= 0) {
+        out[c].status = MI_LP_PROPAGATE_INFEASIBLE;
+        out[c].worst = s.worst;
+        out[c].worst_col = s.worst_row;
+        stopped |= uint32_t{1} << c;
+        if (round == 1) {
+          recount |= uint32_t{1} << c;
+        } else {
+          out[c].moves += s.count;
+        }
+      } else if (s.count == 0) {
+        out[c].status = MI_LP_PROPAGATE_FIXPOINT;
+        stopped |= uint32_t{1} << c;
+      } else {
+        out[c].moves += s.count;
+      }
+    }
+    if (recount != 0) {
+      summarise(moved_keys);
+      for (int c = 0; c < kp; ++c) {
+        if ((recount >> c) & 1u) out[c].moves += host_summaries[c].count;
+      }
+    }
+  }
+  record.panels += 1;
+  record.width = width;
+  record.columns = sink.long_columns ? kPanelLongColumns : kPanelShortColumns;
+  if (sink.tightened == nullptr) {
+    Check(milp_launch::panel_deinterleave(width, w.cols.get(), n, kp, w.flat.get(), n, S(stream_)),
+          "bound propagate de-interleave");
+    Check(milp_launch::panel_deinterleave(width, w.cols_upper.get(), n, kp, w.flat.get() + down, n,
+                                          S(stream_)),
+          "bound propagate de-interleave");
+    timer->Launched();
+    Check(hipMemcpyAsync(sink.final_ubs + size_t(first) * n, w.flat.get() + down,
+                         down * sizeof(double), hipMemcpyDeviceToHost, S(stream_)),
+          "D2H");
+    Download(sink.final_lbs + size_t(first) * n, w.flat.get(), down * sizeof(double));
+    timer->Downloaded();
+    record.bytes_down += 16 * int64_t(down);
+    return;
+  }
+  milp_kernels::PropagateChangedArgs changed{};
+  changed.lower = w.cols.get();
+  changed.upper = w.cols_upper.get();
+  changed.base_lb = w.base.get();
+  changed.base_ub = w.base_upper.get();
+  changed.num_cols = n;
+  changed.kp = kp;
+  changed.tolerance = params.tolerance;
+  changed.keys = apply.keys;
+  Check(milp_launch::propagate_changed_keys(width, changed, S(stream_)),
+        "bound propagate changed keys");
+  PanelKeptColumns(first, kp, width, changed.keys, changed.lower, changed.upper, sink.lists, timer,
+                   sink.tightened, &record.kept, &record.bytes_down, "bound propagated columns");
+  for (int c = 0; c < kp; ++c) {
+    out[c].kept = static_cast<int32_t>(sink.tightened->summaries[first + c].count);
+  }
+}
+
+void DeviceLp::PropagateWithoutRows(const PropagateParams& params, int n, double* l, double* u,
+                                    mi_lp_propagation* summary) {
+  *summary = kPropagationStart;
+  for (int round = 1; round <= params.max_rounds; ++round) {
+    int64_t moves = 0;
+    double worst = 0.0;
+    int worst_col = -1;
+    for (int c = 0; c < n; ++c) {  // without rows the implied bounds are the own ones
+      double nl = l[c];
+      double nu = u[c];
+      if (params.is_integer != nullptr && params.is_integer[c] != 0) {
+        nl = std::ceil(nl - params.integrality_tolerance) + 0.0;
+        nu = std::floor(nu + params.integrality_tolerance) + 0.0;
+      }
+      if ((nl - l[c] > params.tolerance) || (u[c] - nu > params.tolerance)) {
+        l[c] = nl;
+        u[c] = nu;
+        ++moves;
+      }
+      const double cross = l[c] - u[c];
+      if (cross > params.tolerance && cross > worst) {
+        worst = cross;
+        worst_col = c;
+      }
+    }
+    summary->rounds = round;
+    summary->moves += moves;
+    if (worst_col >= 0) {
+      summary->status = MI_LP_PROPAGATE_INFEASIBLE;
+      summary->worst = worst;
+      summary->worst_col = worst_col;
+      return;
+    }
+    if (moves == 0) {
+      summary->status = MI_LP_PROPAGATE_FIXPOINT;
+      return;
+    }
+  }
+}
+
+bool DeviceLp::BoundPropagateBegin(int k, const PropagateParams& params, const double* row_lb,
+                                   const double* row_ub, bool lists, PropagatedColumns* out,
+                                   mi_lp_propagation* summaries, RowPanelSink* sink) {
+  PanelWorkspace& w = *panel_;
+  w.last_bound_propagate = LastBoundPropagate();
+  w.last_bound_propagate.lists = lists;
+  const size_t sets = size_t(std::max(k, 0));
+  if (out != nullptr) {
+    out->lists.col_starts.assign(lists ? sets + 1 : 0, 0);
+    out->lists.cols.clear();
+    out->lists.new_lbs.clear();
+    out->lists.new_ubs.clear();
+    out->lists.summaries.assign(sets, mi_lp_point_violations{0, 0.0, -1, 0});
+    out->summaries.assign(sets, kPropagationStart);
+    summaries = out->summaries.data();
+  } else {
+    std::fill(summaries, summaries + sets, kPropagationStart);
+  }
+  if (!PanelImpliedSetup(k, row_lb, row_ub, sink)) return false;
+  const int n = n_total_ - m_;
+  w.last_bound_propagate.bytes_up = 16 * int64_t(m_);
+  if (params.is_integer != nullptr) {
+    Upload(w.is_integer.Reserve(size_t(n), "panel integer columns"), params.is_integer, size_t(n));
+    w.last_bound_propagate.bytes_up += n;
+  }
+  sink->propagate = &params;
+  sink->propagation = summaries;
+  sink->tolerance = params.tolerance;
+  sink->tightened = out != nullptr ? &out->lists : nullptr;
+  sink->lists = lists;
+  return true;
+}
+
+void DeviceLp::BoundPropagatePanel(const double* lbs, const double* ubs, int k,
+                                   const PropagateParams& params, const double* row_lb,
+                                   const double* row_ub, double* new_lbs, double* new_ubs,
+                                   mi_lp_propagation* summaries) {
+  const int n = n_total_ - m_;
+  RowPanelSink sink;
+  if (BoundPropagateBegin(k, params, row_lb, row_ub, false, nullptr, summaries, &sink)) {
+    DeviceOp("bound propagate panel");
+    sink.final_lbs = new_lbs;
+    sink.final_ubs = new_ubs;
+    RowPanels(lbs, ubs, k, sink);
+    panel_->last_bound_propagate.bytes_up += 16 * int64_t(k) * n;
+    DeviceOp("bound propagate panel done");
+  } else {
+    for (int j = 0; j < k; ++j) {
+      std::copy(lbs + size_t(j) * n, lbs + size_t(j + 1) * n, new_lbs + size_t(j) * n);
+      std::copy(ubs + size_t(j) * n, ubs + size_t(j + 1) * n, new_ubs + size_t(j) * n);
+      PropagateWithoutRows(params, n, new_lbs + size_t(j) * n, new_ubs + size_t(j) * n,
+                           &summaries[j]);
+    }
+  }
+  for (int j = 0; j < k; ++j) {
+    const size_t at = size_t(j) * n;
+    summaries[j].kept = ChangedColumns(new_lbs + at, new_ubs + at, lbs + at, ubs + at, n);
+  }
+}
+
+void DeviceLp::BoundPropagatePanelFrom(const double* base_lb, const double* base_ub, int k,
+                                       const int64_t* starts, const int32_t* cols,
+                                       const double* ov_lbs, const double* ov_ubs,
+                                       const PropagateParams& params, const double* row_lb,
+                                       const double* row_ub, double* new_lbs, double* new_ubs,
+                                       mi_lp_propagation* summaries) {
+  const int n = n_total_ - m_;
+  RowPanelSink sink;
+  const bool launch =
+      BoundPropagateBegin(k, params, row_lb, row_ub, false, nullptr, summaries, &sink);
+  if (launch) {
+    DeviceOp("bound propagate panel from");
+    sink.final_lbs = new_lbs;
+    sink.final_ubs = new_ubs;
+    sink.from_base = true;
+    panel_->last_bound_propagate.bytes_up +=
+        RowPanelsFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, sink);
+    DeviceOp("bound propagate panel from done");
+  }
+  std::vector<double> l(size_t(std::max(n, 0))), u(size_t(std::max(n, 0)));
+  for (int j = 0; j < k; ++j) {
+    const size_t at = size_t(j) * n;
+    MaterialiseSet(base_lb, base_ub, n, j, starts, cols, ov_lbs, ov_ubs, l.data(), u.data());
+    if (!launch) {
+      std::copy(l.begin(), l.end(), new_lbs + at);
+      std::copy(u.begin(), u.end(), new_ubs + at);
+      PropagateWithoutRows(params, n, new_lbs + at, new_ubs + at, &summaries[j]);
+    }
+    summaries[j].kept = ChangedColumns(new_lbs + at, new_ubs + at, l.data(), u.data(), n);
+  }
+}
+
+void DeviceLp::BoundPropagatedColumnsFrom(const double* base_lb, const double* base_ub, int k,
+                                          const int64_t* starts, const int32_t* cols,
+                                          const double* ov_lbs, const double* ov_ubs,
+                                          const PropagateParams& params, const double* row_lb,
+                                          const double* row_ub, bool lists,
+                                          PropagatedColumns* out) {
+  RowPanelSink sink;
+  if (BoundPropagateBegin(k, params, row_lb, row_ub, lists, out, nullptr, &sink)) {
+    DeviceOp("bound propagated columns from");
+    sink.from_base = true;
+    panel_->last_bound_propagate.bytes_up +=
+        RowPanelsFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, sink);
+    DeviceOp("bound propagated columns from done");
+    return;
+  }
+  // Without rows: the rule and the keep rule on the host.
+  const int n = n_total_ - m_;
+  std::vector<double> l(size_t(std::max(n, 0))), u(size_t(std::max(n, 0)));
+  for (int j = 0; j < k; ++j) {
+    MaterialiseSet(base_lb, base_ub, n, j, starts, cols, ov_lbs, ov_ubs, l.data(), u.data());
+    PropagateWithoutRows(params, n, l.data(), u.data(), &out->summaries[j]);
+    int32_t kept = 0;
+    for (int c = 0; c < n; ++c) {
+      if (!(l[c] - u[c] > params.tolerance) && SameBits(l[c], base_lb[c]) &&
+          SameBits(u[c], base_ub[c])) {
+        continue;
+      }
+      ++kept;
+      if (!lists) continue;
+      out->lists.cols.push_back(c);
+      out->lists.new_lbs.push_back(l[c]);
+      out->lists.new_ubs.push_back(u[c]);
+    }
+    out->summaries[j].kept = kept;
+    if (lists) out->lists.col_starts[j + 1] = out->lists.col_starts[j] + kept;
+  }
 }
 
 }  // namespace milp

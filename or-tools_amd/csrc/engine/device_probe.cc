@@ -650,6 +650,112 @@ int LastBoundImplied(mi_devop* h, mi_devop_bound_implied* out) {
   });
 }
 
+milp::DeviceLp::PropagateParams CheckPropagateParams(const mi_devop* h, const char* name,
+                                                     const mi_devop_propagate_params* p,
+                                                     const double* row_lb, const double* row_ub) {
+  if (p == nullptr) throw milp::DeviceError(std::string(name) + ": no parameters");
+  CheckRowBounds(h, name, row_lb, row_ub, p->tolerance);
+  if (p->max_rounds < 1 || !(p->integrality_tolerance >= 0.0) ||
+      !(p->integrality_tolerance < 0.5)) {
+    throw milp::DeviceError(std::string(name) + ": bad rounds or integrality tolerance");
+  }
+  return milp::DeviceLp::PropagateParams{p->is_integer, p->tolerance, p->integrality_tolerance,
+                                         p->max_rounds};
+}
+
+static_assert(sizeof(mi_devop_propagation) == sizeof(mi_lp_propagation) &&
+                  sizeof(mi_lp_propagation) == 32 &&
+                  offsetof(mi_devop_propagation, moves) == offsetof(mi_lp_propagation, moves) &&
+                  offsetof(mi_devop_propagation, worst) == offsetof(mi_lp_propagation, worst) &&
+                  offsetof(mi_devop_propagation, worst_col) ==
+                      offsetof(mi_lp_propagation, worst_col) &&
+                  offsetof(mi_devop_propagation, kept) == offsetof(mi_lp_propagation, kept),
+              "mi_lp_devop.h restates mi_lp_propagation");
+
+int BoundPropagatePanel(mi_devop* h, const double* lbs, const double* ubs, int k,
+                        const mi_devop_propagate_params* params, const double* row_lb,
+                        const double* row_ub, double* new_lbs, double* new_ubs,
+                        mi_devop_propagation* summaries) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::PropagateParams p =
+        CheckPropagateParams(h, "bound_propagate_panel", params, row_lb, row_ub);
+    if (summaries == nullptr) throw milp::DeviceError("bound_propagate_panel: no summaries");
+    h->dev.BoundPropagatePanel(lbs, ubs, k, p, row_lb, row_ub, new_lbs, new_ubs,
+                               reinterpret_cast<mi_lp_propagation*>(summaries));
+  });
+}
+
+int BoundPropagatePanelFrom(mi_devop* h, const double* base_lb, const double* base_ub, int k,
+                            const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                            const double* ov_ubs, const mi_devop_propagate_params* params,
+                            const double* row_lb, const double* row_ub, double* new_lbs,
+                            double* new_ubs, mi_devop_propagation* summaries) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::PropagateParams p =
+        CheckPropagateParams(h, "bound_propagate_panel_from", params, row_lb, row_ub);
+    if (summaries == nullptr) throw milp::DeviceError("bound_propagate_panel_from: no summaries");
+    CheckBoundOverrides(h, "bound_propagate_panel_from", k, starts, cols, ov_lbs, ov_ubs);
+    h->dev.BoundPropagatePanelFrom(base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, p, row_lb,
+                                   row_ub, new_lbs, new_ubs,
+                                   reinterpret_cast<mi_lp_propagation*>(summaries));
+  });
+}
+
+int BoundPropagatedColumnsFrom(mi_devop* h, const double* base_lb, const double* base_ub, int k,
+                               const int64_t* starts, const int32_t* cols_in,
+                               const double* ov_lbs, const double* ov_ubs,
+                               const mi_devop_propagate_params* params, const double* row_lb,
+                               const double* row_ub, int64_t* col_starts, int32_t* cols,
+                               double* new_lbs, double* new_ubs, int64_t capacity,
+                               mi_devop_propagation* summaries) {
+  const char* name = "bound_propagated_columns_from";
+  bool too_large = false;
+  const int rc = Guard(h, [&] {
+    const milp::DeviceLp::PropagateParams p =
+        CheckPropagateParams(h, name, params, row_lb, row_ub);
+    if (col_starts == nullptr && summaries == nullptr) {
+      throw milp::DeviceError(std::string(name) + ": no outputs");
+    }
+    CheckBoundOverrides(h, name, k, starts, cols_in, ov_lbs, ov_ubs);
+    milp::DeviceLp::PropagatedColumns result;
+    h->dev.BoundPropagatedColumnsFrom(base_lb, base_ub, k, starts, cols_in, ov_lbs, ov_ubs, p,
+                                      row_lb, row_ub, col_starts != nullptr, &result);
+    if (col_starts != nullptr) {
+      const int64_t kept = result.lists.col_starts.back();
+      if (kept > capacity) {
+        too_large = true;
+        throw milp::DeviceError(std::string(name) + ": " + std::to_string(kept) +
+                                " entries, capacity " + std::to_string(capacity));
+      }
+      std::memcpy(col_starts, result.lists.col_starts.data(),
+                  result.lists.col_starts.size() * sizeof(int64_t));
+      if (kept > 0) {
+        std::memcpy(cols, result.lists.cols.data(), size_t(kept) * sizeof(int32_t));
+        std::memcpy(new_lbs, result.lists.new_lbs.data(), size_t(kept) * sizeof(double));
+        std::memcpy(new_ubs, result.lists.new_ubs.data(), size_t(kept) * sizeof(double));
+      }
+    }
+    if (summaries != nullptr && k > 0) {
+      std::memcpy(summaries, result.summaries.data(), size_t(k) * sizeof(*summaries));
+    }
+  });
+  return too_large ? int{MI_DEVOP_CAPACITY} : rc;
+}
+
+int LastBoundPropagate(mi_devop* h, mi_devop_bound_propagate* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastBoundPropagate p = h->dev.last_bound_propagate();
+    out->panels = p.panels;
+    out->width = p.width;
+    out->columns = p.columns;
+    out->lists = p.lists ? 1 : 0;
+    out->rounds = p.rounds;
+    out->kept = p.kept;
+    out->bytes_up = p.bytes_up;
+    out->bytes_down = p.bytes_down;
+  });
+}
+
 static_assert(sizeof(mi_devop_point_violations) == sizeof(mi_lp_point_violations) &&
                   offsetof(mi_devop_point_violations, worst_row) ==
                       offsetof(mi_lp_point_violations, worst_row),
@@ -696,4 +802,7 @@ extern "C" const mi_devop_api mi_devop_table = {
     BoundImpliedPanel, BoundImpliedPanelFrom,
     BoundTightenedPanel, BoundTightenedPanelFrom,
     LastBoundImplied,
+    BoundPropagatePanel, BoundPropagatePanelFrom,
+    BoundPropagatedColumnsFrom,
+    LastBoundPropagate,
 };

@@ -5728,6 +5728,10 @@ struct mi_lp {
   // that built them: a fourth store.
   milp::DeviceLp::TightenedColumns tightened_columns;
   bool tightened_columns_stored = false;
+  // Likewise the lists of the last mi_lp_bound_propagated_columns_from call
+  // that built them: a fifth store.
+  milp::DeviceLp::TightenedColumns propagated_columns;
+  bool propagated_columns_stored = false;
   milp::GlopParameters params;
   milp::LinearProgram lp;
   int device = 0;
@@ -6069,6 +6073,7 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t*
   h->violated_rows_stored = false;  // mi_lp_get_violated_rows: likewise
   h->infeasible_rows_stored = false;  // mi_lp_get_infeasible_rows: likewise
   h->tightened_columns_stored = false;  // mi_lp_get_tightened_columns: likewise
+  h->propagated_columns_stored = false;  // mi_lp_get_propagated_columns: likewise
   if ((n > 0 && (clb == nullptr || cub == nullptr || obj == nullptr)) ||
       (m > 0 && (rlb == nullptr || rub == nullptr))) {
     return MI_LP_ERROR_NULL;
@@ -6758,6 +6763,113 @@ int mi_lp_get_tightened_columns(const mi_lp* h, int32_t* cols, double* new_lbs,
     std::memcpy(cols, h->tightened_columns.cols.data(), kept * sizeof(int32_t));
     std::memcpy(new_lbs, h->tightened_columns.new_lbs.data(), kept * sizeof(double));
     std::memcpy(new_ubs, h->tightened_columns.new_ubs.data(), kept * sizeof(double));
+  }
+  return MI_LP_OK;
+}
+
+namespace {
+// The argument checks the three propagate calls add to CheckScreeningArgs.
+bool ValidPropagateArgs(double integrality_tolerance, int32_t max_rounds) {
+  return max_rounds >= 1 && integrality_tolerance >= 0.0 && integrality_tolerance < 0.5;
+}
+}  // namespace
+
+int mi_lp_bound_propagate(mi_lp* h, const double* lbs, const double* ubs, int32_t k,
+                          const uint8_t* is_integer, const double* row_lb, const double* row_ub,
+                          double tolerance, double integrality_tolerance, int32_t max_rounds,
+                          double* new_lbs, double* new_ubs, mi_lp_propagation* summaries) {
+  if (h == nullptr || lbs == nullptr || ubs == nullptr || new_lbs == nullptr ||
+      new_ubs == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  if (!ValidPropagateArgs(integrality_tolerance, max_rounds)) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&] {
+    std::vector<mi_lp_propagation> own(summaries == nullptr ? size_t(k) : 0);
+    const milp::DeviceLp::PropagateParams params{is_integer, tolerance, integrality_tolerance,
+                                                 max_rounds};
+    h->simplex.device().BoundPropagatePanel(lbs, ubs, k, params, row_lb, row_ub, new_lbs, new_ubs,
+                                            summaries == nullptr ? own.data() : summaries);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_bound_propagate_from(mi_lp* h, const double* base_lb, const double* base_ub, int32_t k,
+                               const int64_t* starts, const int32_t* cols, const double* ov_lbs,
+                               const double* ov_ubs, const uint8_t* is_integer,
+                               const double* row_lb, const double* row_ub, double tolerance,
+                               double integrality_tolerance, int32_t max_rounds, double* new_lbs,
+                               double* new_ubs, mi_lp_propagation* summaries) {
+  if (h == nullptr || base_lb == nullptr || base_ub == nullptr || starts == nullptr ||
+      new_lbs == nullptr || new_ubs == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  if (!ValidPropagateArgs(integrality_tolerance, max_rounds)) return MI_LP_ERROR_INVALID_PROBLEM;
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&]() -> int {
+    const int bad_overrides = CheckBoundOverrides(h, k, starts, cols, ov_lbs, ov_ubs);
+    if (bad_overrides != MI_LP_OK) return bad_overrides;
+    std::vector<mi_lp_propagation> own(summaries == nullptr ? size_t(k) : 0);
+    const milp::DeviceLp::PropagateParams params{is_integer, tolerance, integrality_tolerance,
+                                                 max_rounds};
+    h->simplex.device().BoundPropagatePanelFrom(
+        base_lb, base_ub, k, starts, cols, ov_lbs, ov_ubs, params, row_lb, row_ub, new_lbs,
+        new_ubs, summaries == nullptr ? own.data() : summaries);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_bound_propagated_columns_from(mi_lp* h, const double* base_lb, const double* base_ub,
+                                        int32_t k, const int64_t* starts, const int32_t* cols,
+                                        const double* ov_lbs, const double* ov_ubs,
+                                        const uint8_t* is_integer, const double* row_lb,
+                                        const double* row_ub, double tolerance,
+                                        double integrality_tolerance, int32_t max_rounds,
+                                        int64_t* col_starts, mi_lp_propagation* summaries) {
+  if (h == nullptr || base_lb == nullptr || base_ub == nullptr || starts == nullptr ||
+      (col_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  const int bad = CheckScreeningArgs(h, k, &row_lb, &row_ub, tolerance);
+  if (bad != MI_LP_OK) return bad;
+  if (!ValidPropagateArgs(integrality_tolerance, max_rounds)) return MI_LP_ERROR_INVALID_PROBLEM;
+  return PanelCall(h, [&]() -> int {
+    const int bad_overrides = CheckBoundOverrides(h, k, starts, cols, ov_lbs, ov_ubs);
+    if (bad_overrides != MI_LP_OK) return bad_overrides;
+    milp::DeviceLp::PropagatedColumns result;
+    const milp::DeviceLp::PropagateParams params{is_integer, tolerance, integrality_tolerance,
+                                                 max_rounds};
+    h->simplex.device().BoundPropagatedColumnsFrom(base_lb, base_ub, k, starts, cols, ov_lbs,
+                                                   ov_ubs, params, row_lb, row_ub,
+                                                   col_starts != nullptr, &result);
+    if (summaries != nullptr) {
+      std::copy(result.summaries.begin(), result.summaries.end(), summaries);
+    }
+    if (col_starts != nullptr) {
+      std::copy(result.lists.col_starts.begin(), result.lists.col_starts.end(), col_starts);
+      result.lists.summaries.clear();
+      h->propagated_columns = std::move(result.lists);
+      h->propagated_columns_stored = true;
+    }
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_get_propagated_columns(const mi_lp* h, int32_t* cols, double* new_lbs,
+                                 double* new_ubs) {
+  if (h == nullptr || cols == nullptr || new_lbs == nullptr || new_ubs == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->propagated_columns_stored) return MI_LP_ERROR_STATE;
+  const size_t kept = h->propagated_columns.cols.size();
+  if (kept > 0) {
+    std::memcpy(cols, h->propagated_columns.cols.data(), kept * sizeof(int32_t));
+    std::memcpy(new_lbs, h->propagated_columns.new_lbs.data(), kept * sizeof(double));
+    std::memcpy(new_ubs, h->propagated_columns.new_ubs.data(), kept * sizeof(double));
   }
   return MI_LP_OK;
 }

@@ -245,6 +245,48 @@ struct ImpliedGatherArgs {
   double* out_upper;
 };
 
+// One round of bound propagation applied to a panel of K bound sets
+// (panel_kernels.hip, propagate_apply; include/mi_lp.h mi_lp_bound_propagate
+// has the rule). new_lower / new_upper are implied_bounds_panel's results of
+// this round, lower / upper the column-interleaved own bounds it read; every
+// (column, set) with v < kp is one thread's:
+//   integer columns round nl up and nu down (integrality_tolerance);
+//   moved columns take (nl, nu) into lower / upper IN PLACE, others keep both;
+//   keys[col * K + v] is -1.0 for a column that neither moved nor crosses, the
+//   crossing amount l' - u' (> tolerance >= 0) for a crossing one, else 0.0:
+//   the input of the kRowRuleKeptKey passes.
+//   moved_keys != nullptr  also 0.0 for a moved column and -1.0 for any other
+//                    (a column that crosses without a move is no move).
+// Bit v of `frozen` is a set that has stopped: its lanes write -1.0 keys and
+// leave the bounds alone.
+struct PropagateApplyArgs {
+  const double* new_lower;  // column-interleaved, num_cols x K
+  const double* new_upper;
+  double* lower;
+  double* upper;
+  const uint8_t* is_integer;  // num_cols, or nullptr: no integer column
+  int num_cols;
+  int kp;  // sets in use (<= K)
+  double tolerance;
+  double integrality_tolerance;
+  uint32_t frozen;
+  double* keys;
+  double* moved_keys;
+};
+// The keys of the propagated lists: per (column, set) -1.0 for a column whose
+// bounds equal base_lb[col] / base_ub[col] in bits and do not cross, the
+// crossing amount lower - upper (> tolerance) for a crossing one, else 0.0.
+struct PropagateChangedArgs {
+  const double* lower;  // column-interleaved, num_cols x K
+  const double* upper;
+  const double* base_lb;  // num_cols each
+  const double* base_ub;
+  int num_cols;
+  int kp;
+  double tolerance;
+  double* keys;
+};
+
 // Where an update-row kernel that emits the list itself puts it: the
 // ascending listed columns, their coefficients and the count, on the device
 // and (optional, null when off) mirrored into mapped host memory.
@@ -653,6 +695,13 @@ hipError_t implied_bounds_panel(int width, bool long_columns,
                                 const milp_kernels::ImpliedBoundsArgs& args, hipStream_t s);
 // After row_violations_panel under kRowRuleKeptKey with lists.
 hipError_t implied_gather(int width, const milp_kernels::ImpliedGatherArgs& args, hipStream_t s);
+// After implied_bounds_panel on the same stream: the round applied to the own
+// bounds in place, and its keys (panel_kernels.hip propagate_apply_panel_kernel).
+hipError_t propagate_apply(int width, const milp_kernels::PropagateApplyArgs& args,
+                           hipStream_t s);
+// The keys of the final bounds against the base (propagate_changed_keys_kernel).
+hipError_t propagate_changed_keys(int width, const milp_kernels::PropagateChangedArgs& args,
+                                  hipStream_t s);
 hipError_t dense_pack(const int64_t* starts, const double* vals, const int32_t* dense_cols,
                       int nd, int m, double* body, double* tail, hipStream_t s);
 hipError_t gather(const int32_t* list, int n, const double* src, double* dst, hipStream_t s);

@@ -28,7 +28,9 @@
 // count, fold and write passes under a second rule, and the implied column
 // bounds over those ranges (implied_bounds_panel_short_kernel /
 // implied_bounds_panel_long_kernel: the column direction again, over the row
-// direction's result), whose filtered form goes through them under a third.
+// direction's result), whose filtered form goes through them under a third;
+// and what turns a round of them into the next (propagate_apply_panel_kernel,
+// propagate_changed_keys_kernel: bound propagation to a fixpoint).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -1005,6 +1007,65 @@ __global__ __launch_bounds__(256) void implied_gather_kernel(ImpliedGatherArgs a
   a.out_upper[start + i] = a.new_upper[from];
 }
 
+// ---------------------------------------------------------------------------
+// Bound propagation to a fixpoint (include/mi_lp.h mi_lp_bound_propagate has
+// the rule): what turns one round's implied bounds into the next round's own
+// bounds, on the interleaved layout. Thread i owns element i = col * K + v of
+// four arrays (nl, nu, l, u) and of the keys: every access is coalesced, a
+// thread reads and writes its own element only, and the launch comes after
+// the phase-2 kernel that read l and u, so the update is in place. No LDS, no
+// barrier, no atomics. Every difference and sum is one rounded operation
+// (-ffp-contract=off); ceil and floor are exact; + 0.0 turns -0.0 into +0.0;
+// an infinity and a NaN pass through all three unchanged.
+template <int K>
+__global__ __launch_bounds__(256) void propagate_apply_panel_kernel(PropagateApplyArgs a) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= static_cast<int64_t>(a.num_cols) * K) return;
+  const int v = static_cast<int>(i % K);
+  if (v >= a.kp) return;
+  if ((a.frozen >> v) & 1u) {
+    a.keys[i] = -1.0;
+    if (a.moved_keys != nullptr) a.moved_keys[i] = -1.0;
+    return;
+  }
+  double nl = a.new_lower[i];
+  double nu = a.new_upper[i];
+  const double l = a.lower[i];
+  const double u = a.upper[i];
+  if (a.is_integer != nullptr && a.is_integer[i / K] != 0) {
+    nl = ceil(nl - a.integrality_tolerance) + 0.0;
+    nu = floor(nu + a.integrality_tolerance) + 0.0;
+  }
+  // inf - inf is NaN and a NaN own bound gives NaN: neither is a move.
+  const bool moved = (nl - l > a.tolerance) || (u - nu > a.tolerance);
+  const double out_l = moved ? nl : l;
+  const double out_u = moved ? nu : u;
+  const double cross = out_l - out_u;
+  const bool crossing = cross > a.tolerance;
+  if (moved) {
+    a.lower[i] = out_l;
+    a.upper[i] = out_u;
+  }
+  a.keys[i] = crossing ? cross : (moved ? 0.0 : -1.0);
+  if (a.moved_keys != nullptr) a.moved_keys[i] = moved ? 0.0 : -1.0;
+}
+
+// The keys of the propagated lists, same ownership: a set's final bounds
+// against the base, in bits, and the crossing columns.
+template <int K>
+__global__ __launch_bounds__(256) void propagate_changed_keys_kernel(PropagateChangedArgs a) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  if (i >= static_cast<int64_t>(a.num_cols) * K) return;
+  if (static_cast<int>(i % K) >= a.kp) return;
+  const double l = a.lower[i];
+  const double u = a.upper[i];
+  const int64_t col = i / K;
+  const bool changed = __double_as_longlong(l) != __double_as_longlong(a.base_lb[col]) ||
+                       __double_as_longlong(u) != __double_as_longlong(a.base_ub[col]);
+  const double cross = l - u;
+  a.keys[i] = cross > a.tolerance ? cross : (changed ? 0.0 : -1.0);
+}
+
 }  // namespace milp_kernels
 
 namespace milp_launch {
@@ -1108,6 +1169,25 @@ hipError_t implied_gather(int width, const ImpliedGatherArgs& args, hipStream_t 
   const dim3 grid(panel_div_up(args.num_cols, 256), args.kp);
   return for_panel_width(width, [&](auto w) {
     implied_gather_kernel<decltype(w)::value><<<grid, 256, 0, s>>>(args);
+  });
+}
+
+hipError_t propagate_apply(int width, const PropagateApplyArgs& args, hipStream_t s) {
+  if (args.num_cols <= 0 || args.kp <= 0) return hipSuccess;
+  if (args.kp > 32) return hipErrorInvalidValue;  // `frozen` has 32 bits
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    const int blocks = panel_div_up(static_cast<long>(args.num_cols) * K, 256);
+    propagate_apply_panel_kernel<K><<<blocks, 256, 0, s>>>(args);
+  });
+}
+
+hipError_t propagate_changed_keys(int width, const PropagateChangedArgs& args, hipStream_t s) {
+  if (args.num_cols <= 0 || args.kp <= 0) return hipSuccess;
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    const int blocks = panel_div_up(static_cast<long>(args.num_cols) * K, 256);
+    propagate_changed_keys_kernel<K><<<blocks, 256, 0, s>>>(args);
   });
 }
 

@@ -188,6 +188,8 @@ EXPORTED_SYMBOLS = [
     "mi_lp_bound_implied_bounds", "mi_lp_bound_implied_bounds_from",
     "mi_lp_bound_tightened_columns", "mi_lp_bound_tightened_columns_from",
     "mi_lp_get_tightened_columns",
+    "mi_lp_bound_propagate", "mi_lp_bound_propagate_from",
+    "mi_lp_bound_propagated_columns_from", "mi_lp_get_propagated_columns",
     "mi_mps_read_file", "mi_mps_parse_string", "mi_mps_error", "mi_mps_dims", "mi_mps_get",
     "mi_mps_name", "mi_mps_col_name", "mi_mps_row_name", "mi_mps_free",
     "mi_lp_solver_params_default", "mi_lp_scale", "mi_lp_solver_solve",

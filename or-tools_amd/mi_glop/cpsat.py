@@ -402,6 +402,24 @@ def tightened_overrides(result):
             for s, e in zip(col_starts[:-1], col_starts[1:])]
 
 
+def propagate_branches(handle, trail, x, cols, int_cols, max_rounds, tolerance=0.0,
+                       integrality_tolerance=0.0):
+    """The children of a node (branch_overrides(trail, x, cols)) propagated to
+    a fixpoint on the GPU before any of them is solved
+    (LpHandle.propagated_columns_from; int_cols are rounded inward each
+    round). Returns (overrides, summaries): overrides[j] = (cols, new_lbs,
+    new_ubs) is child j's complete override list relative to the trail's
+    bounds, in branch_lps order, and summaries[j] its engine.PROPAGATION
+    record; a child with status engine.PROPAGATE_INFEASIBLE needs no LP."""
+    base_lb, base_ub, overrides = branch_overrides(trail, x, cols)
+    is_integer = np.zeros(len(base_lb), np.uint8)
+    is_integer[np.asarray(list(int_cols), dtype=np.int64)] = 1
+    result = handle.propagated_columns_from(
+        base_lb, base_ub, overrides, max_rounds, is_integer=is_integer, tolerance=tolerance,
+        integrality_tolerance=integrality_tolerance)
+    return tightened_overrides(result), result[4]
+
+
 def fold_node(trail, x, cols, results):
     """Folds batched branch results (MiLpResult per branch LP, in branch_lps
     order) with BranchOnVar's decisions, column by column. Returns a summary:

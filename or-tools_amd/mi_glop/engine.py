@@ -32,6 +32,11 @@ SIMPLEX_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, cty
 POINT_VIOLATIONS = np.dtype([("count", np.int64), ("worst", np.float64),
                              ("worst_row", np.int32), ("reserved", np.int32)])
 assert POINT_VIOLATIONS.itemsize == 24
+# mi_lp_propagation (include/mi_lp.h) as a numpy record.
+PROPAGATION = np.dtype([("status", np.int32), ("rounds", np.int32), ("moves", np.int64),
+                        ("worst", np.float64), ("worst_col", np.int32), ("kept", np.int32)])
+assert PROPAGATION.itemsize == 32
+PROPAGATE_ROUND_LIMIT, PROPAGATE_FIXPOINT, PROPAGATE_INFEASIBLE = 0, 1, 2
 
 
 def build(jobs=8):
@@ -146,6 +151,14 @@ def lib():
     L.mi_lp_bound_tightened_columns_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 6 + [
         ctypes.c_double, vp, vp]
     L.mi_lp_get_tightened_columns.argtypes = [vp, vp, vp, vp]
+    _rounds = [ctypes.c_double, ctypes.c_double, ctypes.c_int32]
+    L.mi_lp_bound_propagate.argtypes = [vp, vp, vp, ctypes.c_int32, vp, vp, vp] + _rounds + [
+        vp, vp, vp]
+    L.mi_lp_bound_propagate_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 7 + _rounds + [
+        vp, vp, vp]
+    L.mi_lp_bound_propagated_columns_from.argtypes = [vp, vp, vp, ctypes.c_int32] + [vp] * 7 + \
+        _rounds + [vp, vp]
+    L.mi_lp_get_propagated_columns.argtypes = [vp, vp, vp, vp]
     L.mi_lp_solver_params_default.argtypes = [ctypes.POINTER(abi.MiLpSolverParams)]
     L.mi_lp_scale.argtypes = [ctypes.POINTER(abi.MiLpSolverParams), ctypes.c_int32,
                               ctypes.c_int32] + [vp] * 14
@@ -879,6 +892,82 @@ class LpHandle:
         args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
         return self._tightened("bound_tightened_columns_from", k, lists, args, row_lb, row_ub,
                                tolerance)
+
+    def _propagate_args(self, max_rounds, is_integer, row_lb, row_ub, tolerance,
+                        integrality_tolerance):
+        """The arguments the three propagate calls share, between the sets and
+        the outputs, and the arrays behind the pointers."""
+        lb, ub = self._row_bounds(row_lb, "row_lb"), self._row_bounds(row_ub, "row_ub")
+        if is_integer is not None:
+            is_integer = np.ascontiguousarray(np.asarray(is_integer) != 0, dtype=np.uint8)
+            if is_integer.shape != (self.lp.n,):
+                raise ValueError(f"is_integer must hold {self.lp.n} values")
+        keep = (is_integer, lb, ub)
+        return (None if is_integer is None or self.lp.n == 0 else _p(is_integer),
+                None if lb is None else _p(lb), None if ub is None else _p(ub),
+                ctypes.c_double(tolerance), ctypes.c_double(integrality_tolerance),
+                int(max_rounds)), keep
+
+    def _propagate(self, name, k, args, common):
+        n = self.lp.n
+        new_lbs = np.zeros((max(k, 1), max(n, 1)), np.float64)
+        new_ubs = np.zeros((max(k, 1), max(n, 1)), np.float64)
+        summaries = np.zeros(max(k, 1), PROPAGATION)
+        self._call(name, *args, *common, _p(new_lbs), _p(new_ubs), _p(summaries))
+        return new_lbs[:k, :n], new_ubs[:k, :n], summaries[:k]
+
+    def propagate_bounds(self, lbs, ubs, max_rounds, is_integer=None, row_lb=None, row_ub=None,
+                         tolerance=0.0, integrality_tolerance=0.0):
+        """Node propagation on the GPU: implied_bounds repeated per bound set
+        (lbs, ubs: (k, n)) until no column moves by more than tolerance, a
+        column crosses by more than it, or max_rounds; columns with a non-zero
+        is_integer (n values, None: no integer column) are rounded inward
+        within integrality_tolerance each round. Returns (new_lbs, new_ubs,
+        summaries): the final bounds, each (k, n), and one PROPAGATION record
+        per set (status PROPAGATE_ROUND_LIMIT / _FIXPOINT / _INFEASIBLE,
+        rounds, moves, worst and worst_col of a crossing, kept = columns that
+        differ in bits from the input). The rule is include/mi_lp.h
+        mi_lp_bound_propagate; it is not outward-rounded."""
+        lbs, ubs, k = self._bound_sets(lbs, ubs)
+        common, _keep = self._propagate_args(max_rounds, is_integer, row_lb, row_ub, tolerance,
+                                             integrality_tolerance)
+        return self._propagate("bound_propagate", k, (_p(lbs), _p(ubs), k), common)
+
+    def propagate_bounds_from(self, base_lb, base_ub, overrides, max_rounds, is_integer=None,
+                              row_lb=None, row_ub=None, tolerance=0.0,
+                              integrality_tolerance=0.0):
+        """propagate_bounds of the sets base + overrides (as
+        bound_activity_ranges_from takes them), built on the GPU."""
+        args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
+        common, _keep2 = self._propagate_args(max_rounds, is_integer, row_lb, row_ub, tolerance,
+                                              integrality_tolerance)
+        return self._propagate("bound_propagate_from", k, args, common)
+
+    def propagated_columns_from(self, base_lb, base_ub, overrides, max_rounds, is_integer=None,
+                                row_lb=None, row_ub=None, tolerance=0.0,
+                                integrality_tolerance=0.0, lists=True):
+        """propagate_bounds_from filtered on the GPU: per set the columns whose
+        final bounds differ in bits from the base, or that cross. Returns
+        (col_starts[k+1] int64, cols int32, new_lbs, new_ubs, summaries); set
+        j's list is its complete override list relative to the base
+        (cpsat.tightened_overrides slices it) and summaries[j].kept its length.
+        With lists=False only the summaries come down and the first four are
+        None."""
+        args, k, _keep = self._bound_overrides(base_lb, base_ub, overrides)
+        common, _keep2 = self._propagate_args(max_rounds, is_integer, row_lb, row_ub, tolerance,
+                                              integrality_tolerance)
+        starts = np.zeros(max(k, 1) + 1, np.int64) if lists else None
+        summaries = np.zeros(max(k, 1), PROPAGATION)
+        self._call("bound_propagated_columns_from", *args, *common,
+                   None if starts is None else _p(starts), _p(summaries))
+        if not lists:
+            return None, None, None, None, summaries[:k]
+        kept = int(starts[k])
+        cols = np.zeros(max(1, kept), np.int32)
+        new_lbs = np.zeros(max(1, kept), np.float64)
+        new_ubs = np.zeros(max(1, kept), np.float64)
+        self._call("get_propagated_columns", _p(cols), _p(new_lbs), _p(new_ubs))
+        return starts[:k + 1], cols[:kept], new_lbs[:kept], new_ubs[:kept], summaries[:k]
 
 
 def batch_solve(handles, num_threads=4, progress=None, progress_s=15.0):
