@@ -329,6 +329,94 @@ int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
                                   int64_t* row_starts, double* left_inverses);
 int mi_lp_get_sparse_rows(const mi_lp* h, int32_t* cols, double* vals);
 
+/* The same rows reduced on the GPU to one branching penalty record each: the
+ * Driebeek penalty with Tomlin's integer strengthening, the bound that the
+ * first dual simplex pivot of each child of a branching gives (what a
+ * branch-and-bound host ranks or drops children by before it pays for
+ * mi_lp_batch_solve_bounds). Only 32 bytes per vector come down. Glop's
+ * dictionary has [A | I] x = 0, so the basic variable of row r is
+ * x_B(r) = -sum over non-basic j of alpha_j x_j with alpha = rho^T [A | I],
+ * rho = row r of B^-1: alpha is bit for bit mi_lp_row_combinations' out for
+ * y = rho.
+ *   mi_lp_row_penalties                  out[v] for v < k from alpha = row v of
+ *                                        mi_lp_row_combinations(y) and the caller's d
+ *                                        (n+m reduced costs, minimisation sense), status
+ *                                        (n+m, MI_LP_BASIC .. MI_LP_FREE), unit (n+m steps
+ *                                        of integer columns in LP units, 0 for a
+ *                                        continuous column; NULL: all 0), down_dist[v],
+ *                                        up_dist[v] and pivot_tolerance. Per column col,
+ *                                        in doubles without FMA:
+ *                                        1. BASIC and FIXED_VALUE columns take no part.
+ *                                        2. cost = d > 0 ? d : 0.0 AT_LOWER_BOUND,
+ *                                           d < 0 ? -d : 0.0 AT_UPPER_BOUND, 0.0 FREE.
+ *                                        3. A NaN alpha or d: the column takes part in both
+ *                                           directions with the candidate +0.0 (a NaN only
+ *                                           ever says "not proven").
+ *                                        4. Else, unless fabs(alpha) > pivot_tolerance
+ *                                           (strict), the column takes no part.
+ *                                        5. Else it takes part in the down direction iff
+ *                                           FREE, AT_LOWER_BOUND with alpha > 0 or
+ *                                           AT_UPPER_BOUND with alpha < 0, and in the up
+ *                                           direction iff FREE, AT_LOWER_BOUND with
+ *                                           alpha < 0 or AT_UPPER_BOUND with alpha > 0
+ *                                           (raising a non-basic column by t moves x_B(r)
+ *                                           by -alpha t).
+ *                                        6. Its candidate there is c = dist * (cost /
+ *                                           fabs(alpha)); with unit > 0 then
+ *                                           c = c < cost * unit ? cost * unit : c; a NaN c
+ *                                           (0 * inf, inf / inf) counts as +0.0.
+ *                                        Per direction: the penalty is the smallest
+ *                                        candidate (+inf without one), the column the
+ *                                        lowest one whose candidate equals it (-1 without
+ *                                        one), the count the number of columns that take
+ *                                        part. Candidates are >= +0.0, never -0.0 or NaN,
+ *                                        so the record does not depend on the reduction
+ *                                        order. A count of 0 proves that child infeasible.
+ *                                        With unit all 0 the penalty bounds the child's LP
+ *                                        objective increase (minimisation sense), with
+ *                                        integer steps the child's integer problem.
+ *                                        Everything is the caller's; changes no state.
+ *   mi_lp_branching_penalties            the same for the k BASIC columns cols (structural
+ *                                        or slack) of the current basis: y_j = the values
+ *                                        of GetUnitRowLeftInverse(row of cols[j]) as in
+ *                                        mi_lp_get_tableau_rows (left_inverses: k x m, or
+ *                                        NULL; the same side effects); status =
+ *                                        mi_lp_get_state's; d in the simplex's internal
+ *                                        minimisation sense: for a minimised LP
+ *                                        d[col] = mi_lp_get_reduced_costs[col] (col < n)
+ *                                        and d[n + r] = -mi_lp_get_duals[r]; for a
+ *                                        maximised LP the solver minimises -objective and
+ *                                        the getters return the negated internal values,
+ *                                        so d[col] = -mi_lp_get_reduced_costs[col] and
+ *                                        d[n + r] = +mi_lp_get_duals[r], and the penalties
+ *                                        bound the DECREASE of the maximised objective.
+ *                                        NULL down_dist / up_dist mean v - floor(v) and
+ *                                        ceil(v) - v of the column's current value v
+ *                                        (mi_lp_get_primal; for the slack of row r,
+ *                                        -mi_lp_get_activities[r]). unit: n entries, or
+ *                                        NULL; slacks get 0.
+ * MI_LP_ERROR_NULL: NULL h, y, d, status, cols, out, or (mi_lp_row_penalties)
+ * NULL distances. Before a solve: MI_LP_ERROR_STATE.
+ * MI_LP_ERROR_INVALID_PROBLEM: k < 0, a status outside 0..4, a negative or NaN
+ * pivot_tolerance, a distance or unit that is negative, NaN or infinite, a
+ * column of cols outside [0, n+m) or not BASIC. On every error nothing is
+ * written. k = 0 succeeds and writes nothing. */
+typedef struct mi_lp_branch_penalty {
+  double down;        /* smallest down candidate, +inf when down_count == 0 */
+  double up;
+  int32_t down_col;   /* lowest column attaining it, -1 when down_count == 0 */
+  int32_t up_col;
+  int32_t down_count; /* columns that take part; 0 proves the child infeasible */
+  int32_t up_count;
+} mi_lp_branch_penalty;
+int mi_lp_row_penalties(mi_lp* h, const double* y, int32_t k, const double* d,
+                        const int8_t* status, const double* unit, const double* down_dist,
+                        const double* up_dist, double pivot_tolerance,
+                        mi_lp_branch_penalty* out);
+int mi_lp_branching_penalties(mi_lp* h, const int32_t* cols, int32_t k, const double* down_dist,
+                              const double* up_dist, const double* unit, double pivot_tolerance,
+                              mi_lp_branch_penalty* out, double* left_inverses);
+
 /* The other half: the row sums [A | I] x_j of k candidate points in one call
  * that reads A once per panel of up to 16 points (what a caller reads cut
  * violations and row feasibility of roundings, neighbours or ray combinations

@@ -82,6 +82,27 @@ typedef struct mi_devop_panel_sparse_geometry {
 /* column_dots_panel_sparse: the result needs more than `capacity` entries. */
 enum { MI_DEVOP_CAPACITY = 2 };
 
+/* mi_lp_branch_penalty of include/mi_lp.h, restated so that this header
+ * stands alone. */
+typedef struct mi_devop_branch_penalty {
+  double down;
+  double up;
+  int32_t down_col; /* -1 when down_count == 0 */
+  int32_t up_col;
+  int32_t down_count;
+  int32_t up_count;
+} mi_devop_branch_penalty;
+/* DeviceLp::LastPenalties: the last column_penalties_panel. */
+typedef struct mi_devop_penalties {
+  int32_t sparse; /* as mi_devop_panel */
+  int32_t dense;
+  int32_t panels;
+  int32_t width;
+  int32_t tiles; /* tiles of tile_columns columns per panel (summed over column shards) */
+  int32_t reserved;
+  int64_t bytes_down; /* device-to-host bytes of the call */
+} mi_devop_penalties;
+
 /* DeviceLp::LastColumnDots: the last launch of the column-dot kernels. */
 typedef struct mi_devop_column_dots {
   int32_t mode;         /* DotMode of simplex_kernels.hip: 1 pricing, 5 pricing with dots */
@@ -363,6 +384,16 @@ typedef struct mi_devop_api {
                                        double* new_ubs, int64_t capacity,
                                        mi_devop_propagation* summaries);
   int (*last_bound_propagate)(mi_devop* h, mi_devop_bound_propagate* out);
+  /* Appended after last_bound_propagate. DeviceLp::ColumnPenaltiesPanel (the
+   * rule: include/mi_lp.h mi_lp_row_penalties). y: k x m; d, status: N; unit:
+   * N, or NULL; down_dist, up_dist: k; out: k records. The arguments are
+   * checked here as mi_lp_row_penalties checks them: a bad one is an error
+   * with nothing written and no device error. */
+  int (*column_penalties_panel)(mi_devop* h, const double* y, int k, const double* d,
+                                const int8_t* status, const double* unit,
+                                const double* down_dist, const double* up_dist,
+                                double pivot_tolerance, mi_devop_branch_penalty* out);
+  int (*last_penalties)(mi_devop* h, mi_devop_penalties* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

@@ -208,6 +208,36 @@ class DeviceLp : public DeviceSolver {
   static int PanelTileColumns();
   static int PanelOffsetsStepTiles();
 
+  // The same dots reduced to one branching penalty record per vector
+  // (include/mi_lp.h mi_lp_row_penalties has the rule): out[j] for j < k from
+  // alpha = ColumnDotsPanel's row j, d (N reduced costs), status (N bytes,
+  // MI_LP_BASIC .. MI_LP_FREE, checked by the caller), unit (N, or null: all
+  // 0), down_dist / up_dist (k each) and pivot_tolerance. The dot launches
+  // are ColumnDotsPanel's; then penalties_tile / penalties_fold reduce the
+  // interleaved results on the device and only 32 bytes per vector come
+  // down. d, status, unit and the distances go up once per call. Same
+  // buffers as ColumnDotsPanel plus those and the per-tile partials; the same
+  // solve state is left alone. With column shards each shard reduces its own
+  // columns and the records are merged on the host (the smaller candidate,
+  // the lower global column, the summed counts): the unsharded result in
+  // every bit and index. Synchronizes before it returns.
+  void ColumnPenaltiesPanel(const double* y, int k, const double* d, const uint8_t* status,
+                            const double* unit, const double* down_dist, const double* up_dist,
+                            double pivot_tolerance, mi_lp_branch_penalty* out);
+  // Preconditions: k >= 0, every status in 0..4, pivot_tolerance >= 0 (not
+  // NaN), every distance and unit finite and >= 0. unit may be null.
+  static bool ValidPenaltyArgs(int num_cols, int k, const int8_t* status, const double* unit,
+                               const double* down_dist, const double* up_dist,
+                               double pivot_tolerance);
+  // The last ColumnPenaltiesPanel (test record); last_panel() is not changed
+  // by it.
+  struct LastPenalties {
+    LastPanel panel;
+    int tiles = 0;           // tiles of kPanelTileColumns columns per panel
+    int64_t bytes_down = 0;  // device-to-host bytes of the call
+  };
+  LastPenalties last_penalties() const;
+
   // --- 1 + ||a_j||^2 for relevant j (identity basis) -------------------
   void ColumnSquaredNorms(std::vector<double>* out);
 
@@ -686,6 +716,10 @@ class DeviceLp : public DeviceSolver {
   void ShardedColumnDotsPanel(const double* y, int k, double* out);
   void ShardedColumnDotsPanelSparse(const double* y, int k, double drop_tolerance,
                                     const uint64_t* keep_words, SparseRows* out);
+  void ShardedColumnPenaltiesPanel(const double* y, int k, const double* d,
+                                   const uint8_t* status, const double* unit,
+                                   const double* down_dist, const double* up_dist,
+                                   double pivot_tolerance, mi_lp_branch_penalty* out);
   void ShardedStats();
   void FlushOwnMasks();
   // The panel calls (device_panel.hip): their buffers, timing events and

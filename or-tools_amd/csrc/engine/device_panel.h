@@ -1,5 +1,6 @@
 // The workspace of DeviceLp's panel calls (device_panel.hip): the buffers of
-// ColumnDotsPanel, ColumnDotsPanelSparse, RowSumsPanel, RowSumsPanelFrom,
+// ColumnDotsPanel, ColumnDotsPanelSparse, ColumnPenaltiesPanel, RowSumsPanel,
+// RowSumsPanelFrom,
 // RowViolationsPanel(From), BoundRangesPanel(From),
 // BoundInfeasiblePanel(From), BoundImpliedPanel(From),
 // BoundTightenedPanel(From), BoundPropagatePanel(From) and
@@ -142,6 +143,17 @@ struct PanelWorkspace {
   DeviceBuffer<milp_kernels::PointViolations> summaries;       // kPanelMaxWidth
   PinnedBuffer<milp_kernels::PointViolations> summaries_host;  // kPanelMaxWidth
 
+  // ColumnPenaltiesPanel only: column dots up to the results in `cols`, which
+  // penalties_tile / penalties_fold reduce; `flat` is not used. The per-tile
+  // partials of both directions go into tile_worst (minima), tile_worst_row
+  // (columns) and counts, 2 kp x tiles each (tiles of 256 columns).
+  DeviceBuffer<double> penalty_d;        // reduced costs, N, uploaded once per call
+  DeviceBuffer<uint8_t> penalty_status;  // N, uploaded once per call
+  DeviceBuffer<double> penalty_unit;     // integer steps, N, uploaded once per call (if given)
+  DeviceBuffer<double> penalty_dist;     // down distances (k), then up (k), once per call
+  DeviceBuffer<milp_kernels::BranchPenalty> penalties;       // kPanelMaxWidth
+  PinnedBuffer<milp_kernels::BranchPenalty> penalties_host;  // kPanelMaxWidth
+
   // RowSumsPanelFrom and RowViolationsPanelFrom, uploaded once per call.
   DeviceBuffer<double> base;        // the base point, N
   DeviceBuffer<int64_t> ov_starts;  // k + 1
@@ -159,6 +171,7 @@ struct PanelWorkspace {
 
   DeviceLp::LastPanel last_panel;
   DeviceLp::LastPanelSparse last_panel_sparse;
+  DeviceLp::LastPenalties last_penalties;
   DeviceLp::LastRowPanel last_row_panel;
   DeviceLp::LastRowViolations last_row_violations;
   DeviceLp::LastBoundRanges last_bound_ranges;

@@ -1,5 +1,6 @@
 // DeviceLp's panel calls: k vectors per pass over [A | I] (see device_lp.h).
-// Column dots (ColumnDotsPanel, ColumnDotsPanelSparse), row sums (RowSumsPanel,
+// Column dots (ColumnDotsPanel, ColumnDotsPanelSparse, and their reduction to
+// branching penalties, ColumnPenaltiesPanel), row sums (RowSumsPanel,
 // RowSumsPanelFrom), their violated rows (RowViolationsPanel,
 // RowViolationsPanelFrom) and the activity ranges of bound sets
 // (BoundRangesPanel(From), BoundInfeasiblePanel(From)) with the implied column
@@ -274,6 +275,102 @@ void DeviceLp::ColumnDotsPanelSparse(const double* y, int k, double drop_toleran
     w.last_panel_sparse.bytes_down += int64_t(kp) * 8 + kept * 12;
   });
   DeviceOp("column dots panel sparse done");
+}
+
+static_assert(sizeof(milp_kernels::BranchPenalty) == sizeof(mi_lp_branch_penalty) &&
+                  sizeof(mi_lp_branch_penalty) == 32 &&
+                  offsetof(milp_kernels::BranchPenalty, up) == offsetof(mi_lp_branch_penalty, up) &&
+                  offsetof(milp_kernels::BranchPenalty, down_col) ==
+                      offsetof(mi_lp_branch_penalty, down_col) &&
+                  offsetof(milp_kernels::BranchPenalty, up_count) ==
+                      offsetof(mi_lp_branch_penalty, up_count),
+              "kernel_args.h restates mi_lp_branch_penalty");
+
+DeviceLp::LastPenalties DeviceLp::last_penalties() const { return panel_->last_penalties; }
+
+bool DeviceLp::ValidPenaltyArgs(int num_cols, int k, const int8_t* status, const double* unit,
+                                const double* down_dist, const double* up_dist,
+                                double pivot_tolerance) {
+  if (k < 0 || !(pivot_tolerance >= 0.0)) return false;
+  auto distance = [](double x) { return x >= 0.0 && x < HUGE_VAL; };  // false for a NaN
+  for (int j = 0; j < k; ++j) {
+    if (!distance(down_dist[j]) || !distance(up_dist[j])) return false;
+  }
+  for (int c = 0; c < num_cols; ++c) {
+    if (status[c] < MI_LP_BASIC || status[c] > MI_LP_FREE) return false;
+    if (unit != nullptr && !distance(unit[c])) return false;
+  }
+  return true;
+}
+
+void DeviceLp::ColumnPenaltiesPanel(const double* y, int k, const double* d,
+                                    const uint8_t* status, const double* unit,
+                                    const double* down_dist, const double* up_dist,
+                                    double pivot_tolerance, mi_lp_branch_penalty* out) {
+  if (!shards_.empty()) {
+    return ShardedColumnPenaltiesPanel(y, k, d, status, unit, down_dist, up_dist,
+                                       pivot_tolerance, out);
+  }
+  PanelWorkspace& w = *panel_;
+  w.last_penalties = LastPenalties();
+  for (int j = 0; j < k; ++j) {
+    out[j] = mi_lp_branch_penalty{HUGE_VAL, HUGE_VAL, -1, -1, 0, 0};
+  }
+  if (k <= 0 || n_total_ <= 0) return;
+  DeviceOp("column penalties panel");
+  const PanelPlan plan = PanelKernelChoice();
+  const int tiles = (n_total_ + milp_kernels::kPanelTileColumns - 1) /
+                    milp_kernels::kPanelTileColumns;
+  const size_t N = size_t(n_total_);
+  Upload(w.penalty_d.Reserve(N, "panel reduced costs"), d, N * sizeof(double));
+  Upload(w.penalty_status.Reserve(N, "panel statuses"), status, N);
+  if (unit != nullptr) {
+    Upload(w.penalty_unit.Reserve(N, "panel integer steps"), unit, N * sizeof(double));
+  }
+  double* dist = w.penalty_dist.Reserve(2 * size_t(k), "panel distances");
+  Upload(dist, down_dist, size_t(k) * sizeof(double));
+  Upload(dist + k, up_dist, size_t(k) * sizeof(double));
+  w.last_penalties.tiles = tiles;
+  ForEachPanel(k, [&](int first, int kp, int width) {
+    PanelUploadVectors(y, first, kp, width);
+    PanelTimer timer(&w, S(stream_));
+    PanelLaunchDots(plan, kp, width);
+    const size_t partials = 2 * size_t(kp) * tiles;
+    milp_kernels::PenaltyArgs a{};
+    a.in = w.cols.get();
+    a.ncols = n_total_;
+    a.kp = kp;
+    a.tiles = tiles;
+    a.d = w.penalty_d.get();
+    a.status = w.penalty_status.get();
+    a.unit = unit != nullptr ? w.penalty_unit.get() : nullptr;
+    a.down_dist = dist + first;
+    a.up_dist = dist + k + first;
+    a.pivot_tolerance = pivot_tolerance;
+    a.tile_min = w.tile_worst.Reserve(partials, "panel tile minima");
+    a.tile_col = w.tile_worst_row.Reserve(partials, "panel tile columns");
+    a.tile_count = w.counts.Reserve(partials, "panel counts");
+    a.out = w.penalties.Reserve(milp_kernels::kPanelMaxWidth, "panel penalties");
+    const milp_kernels::BranchPenalty* host =
+        w.penalties_host.Reserve(milp_kernels::kPanelMaxWidth, "panel penalties");
+    Check(milp_launch::panel_penalties(width, a, S(stream_)), "panel penalties");
+    timer.Launched();
+    Download(w.penalties_host.get(), a.out, size_t(kp) * sizeof(*a.out));
+    timer.Downloaded();
+    for (int v = 0; v < kp; ++v) {
+      const milp_kernels::BranchPenalty& p = host[v];
+      if (p.down_count < 0 || p.down_count > n_total_ || p.up_count < 0 ||
+          p.up_count > n_total_ || p.down_col < -1 || p.down_col >= n_total_ ||
+          p.up_col < -1 || p.up_col >= n_total_) {
+        throw DeviceError("column penalties panel: bad record");
+      }
+      out[first + v] =
+          mi_lp_branch_penalty{p.down, p.up, p.down_col, p.up_col, p.down_count, p.up_count};
+    }
+    PanelRecord(plan, width, &w.last_penalties.panel);
+    w.last_penalties.bytes_down += int64_t(kp) * 32;
+  });
+  DeviceOp("column penalties panel done");
 }
 
 bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const int32_t* cols) {

@@ -756,6 +756,38 @@ int LastBoundPropagate(mi_devop* h, mi_devop_bound_propagate* out) {
   });
 }
 
+int ColumnPenaltiesPanel(mi_devop* h, const double* y, int k, const double* d,
+                         const int8_t* status, const double* unit, const double* down_dist,
+                         const double* up_dist, double pivot_tolerance,
+                         mi_devop_branch_penalty* out) {
+  return Guard(h, [&] {
+    if (!milp::DeviceLp::ValidPenaltyArgs(h->csc.num_cols(), k, status, unit, down_dist, up_dist,
+                                          pivot_tolerance)) {
+      throw milp::DeviceError("column_penalties_panel: bad arguments");
+    }
+    h->dev.ColumnPenaltiesPanel(y, k, d, reinterpret_cast<const uint8_t*>(status), unit,
+                                down_dist, up_dist, pivot_tolerance,
+                                reinterpret_cast<mi_lp_branch_penalty*>(out));
+  });
+}
+
+int LastPenalties(mi_devop* h, mi_devop_penalties* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastPenalties p = h->dev.last_penalties();
+    out->sparse = p.panel.sparse;
+    out->dense = p.panel.dense ? 1 : 0;
+    out->panels = p.panel.panels;
+    out->width = p.panel.width;
+    out->tiles = p.tiles;
+    out->reserved = 0;
+    out->bytes_down = p.bytes_down;
+  });
+}
+
+static_assert(sizeof(mi_devop_branch_penalty) == sizeof(mi_lp_branch_penalty) &&
+                  offsetof(mi_devop_branch_penalty, up_count) ==
+                      offsetof(mi_lp_branch_penalty, up_count),
+              "mi_lp_devop.h restates mi_lp_branch_penalty");
 static_assert(sizeof(mi_devop_point_violations) == sizeof(mi_lp_point_violations) &&
                   offsetof(mi_devop_point_violations, worst_row) ==
                       offsetof(mi_lp_point_violations, worst_row),
@@ -805,4 +837,5 @@ extern "C" const mi_devop_api mi_devop_table = {
     BoundPropagatePanel, BoundPropagatePanelFrom,
     BoundPropagatedColumnsFrom,
     LastBoundPropagate,
+    ColumnPenaltiesPanel, LastPenalties,
 };

@@ -523,6 +523,65 @@ void DeviceLp::ShardedColumnDotsPanelSparse(const double* y, int k, double drop_
   }
 }
 
+// Each block's records over its own columns (d, status and unit cut at the
+// block's first column), merged per vector and direction in block order: the
+// smaller candidate, among equal candidates the earlier block's column (the
+// lower one), the block's first column added; the counts are summed. The
+// parts travel through ExchangeParts like ShardedColumnDotsPanel's.
+void DeviceLp::ShardedColumnPenaltiesPanel(const double* y, int k, const double* d,
+                                           const uint8_t* status, const double* unit,
+                                           const double* down_dist, const double* up_dist,
+                                           double pivot_tolerance, mi_lp_branch_penalty* out) {
+  DeviceGuard guard{device_};
+  LastPenalties& record = panel_->last_penalties;
+  record = LastPenalties();
+  for (int j = 0; j < k; ++j) {
+    out[j] = mi_lp_branch_penalty{HUGE_VAL, HUGE_VAL, -1, -1, 0, 0};
+  }
+  if (k <= 0) return;
+  const int ns = num_shards();
+  std::vector<std::string> parts(ns);
+  std::vector<mi_lp_branch_penalty> part;
+  for (int s = 0; s < ns; ++s) {
+    if (!IsLocalShard(s)) continue;
+    DeviceLp& shard = Shard(s);
+    part.assign(size_t(k), mi_lp_branch_penalty{HUGE_VAL, HUGE_VAL, -1, -1, 0, 0});
+    if (shard.n_total_ > 0) {
+      const int b = shard_begin_[s];
+      shard.ColumnPenaltiesPanel(y, k, d + b, status + b, unit != nullptr ? unit + b : nullptr,
+                                 down_dist, up_dist, pivot_tolerance, part.data());
+      const LastPenalties p = shard.last_penalties();
+      record.panel.Merge(p.panel);
+      record.tiles += p.tiles;
+      record.bytes_down += p.bytes_down;
+    }
+    PartWriter w;
+    w.Put(part);
+    parts[s] = std::move(w.b);
+  }
+  ExchangeParts(&parts);
+  auto merge = [](double* value, int32_t* col, int32_t* count, double other, int32_t other_col,
+                  int32_t other_count, int32_t base) {
+    if (other_count > 0 && (*count == 0 || other < *value)) {
+      *value = other;
+      *col = other_col + base;
+    }
+    *count += other_count;
+  };
+  for (int s = 0; s < ns; ++s) {
+    PartReader r{parts[s]};
+    r.Get(&part);
+    if (part.size() != size_t(k)) throw DeviceError("column split: bad penalties part");
+    const int32_t base = shard_begin_[s];
+    for (int j = 0; j < k; ++j) {
+      const mi_lp_branch_penalty& p = part[j];
+      merge(&out[j].down, &out[j].down_col, &out[j].down_count, p.down, p.down_col,
+            p.down_count, base);
+      merge(&out[j].up, &out[j].up_col, &out[j].up_count, p.up, p.up_col, p.up_count, base);
+    }
+  }
+}
+
 void DeviceLp::ShardedDualBegin(const std::vector<double>& rc,
                                 const std::vector<uint8_t>& colbits,
                                 const std::vector<double>& bound_diff) {

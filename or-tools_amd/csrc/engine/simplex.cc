@@ -6378,6 +6378,91 @@ int mi_lp_get_tableau_rows_sparse(mi_lp* h, const int32_t* rows, int32_t k,
   });
 }
 
+int mi_lp_row_penalties(mi_lp* h, const double* y, int32_t k, const double* d,
+                        const int8_t* status, const double* unit, const double* down_dist,
+                        const double* up_dist, double pivot_tolerance,
+                        mi_lp_branch_penalty* out) {
+  if (h == nullptr || y == nullptr || d == nullptr || status == nullptr ||
+      down_dist == nullptr || up_dist == nullptr || out == nullptr) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (!milp::DeviceLp::ValidPenaltyArgs(h->lp.n + h->lp.m, k, status, unit, down_dist, up_dist,
+                                        pivot_tolerance)) {
+    return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&] {
+    h->simplex.device().ColumnPenaltiesPanel(y, k, d, reinterpret_cast<const uint8_t*>(status),
+                                             unit, down_dist, up_dist, pivot_tolerance, out);
+    return MI_LP_OK;
+  });
+}
+
+int mi_lp_branching_penalties(mi_lp* h, const int32_t* cols, int32_t k, const double* down_dist,
+                              const double* up_dist, const double* unit, double pivot_tolerance,
+                              mi_lp_branch_penalty* out, double* left_inverses) {
+  if (h == nullptr || cols == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  const int n = h->lp.n;
+  const int m = h->lp.m;
+  const int total = n + m;
+  const auto& state = h->simplex.GetState();
+  if (state.size() != size_t(total)) return MI_LP_ERROR_STATE;
+  // The basis row of every basic column; -1: not basic.
+  std::vector<int32_t> row_of(size_t(total), -1);
+  for (int r = 0; r < m; ++r) {
+    const int col = h->simplex.GetBasis(r);
+    if (col >= 0 && col < total) row_of[col] = r;
+  }
+  std::vector<int32_t> rows(size_t(std::max(k, 0)));
+  std::vector<double> down(rows.size()), up(rows.size());
+  for (int32_t j = 0; j < k; ++j) {
+    if (cols[j] < 0 || cols[j] >= total || row_of[cols[j]] < 0) {
+      return MI_LP_ERROR_INVALID_PROBLEM;
+    }
+    rows[j] = row_of[cols[j]];
+    const double v = h->simplex.GetVariableValue(cols[j]);
+    down[j] = down_dist != nullptr ? down_dist[j] : v - std::floor(v);
+    up[j] = up_dist != nullptr ? up_dist[j] : std::ceil(v) - v;
+  }
+  // The simplex minimises -objective of a maximised LP, and the getters
+  // return the negated internal values (Solve()).
+  const bool maximize = h->lp.maximize;
+  const size_t columns = size_t(total);
+  std::vector<int8_t> status(columns);
+  std::vector<double> d(columns);
+  std::vector<double> steps;
+  for (int col = 0; col < total; ++col) status[col] = static_cast<int8_t>(state[col]);
+  for (int col = 0; col < n; ++col) {
+    const double rc = h->simplex.GetReducedCost(col);
+    d[col] = maximize ? -rc : rc;
+  }
+  for (int r = 0; r < m; ++r) {
+    const double dual = h->simplex.GetDualValue(r);
+    d[n + r] = maximize ? dual : -dual;
+  }
+  if (unit != nullptr) {
+    steps.assign(size_t(total), 0.0);
+    std::copy(unit, unit + n, steps.begin());
+  }
+  if (!milp::DeviceLp::ValidPenaltyArgs(total, k, status.data(),
+                                        unit != nullptr ? steps.data() : nullptr, down.data(),
+                                        up.data(), pivot_tolerance)) {
+    return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  if (k == 0) return MI_LP_OK;
+  return PanelCall(h, [&] {
+    std::vector<double> local;
+    const double* y = LeftInverses(h, rows.data(), k, left_inverses, &local);
+    h->simplex.device().ColumnPenaltiesPanel(
+        y, k, d.data(), reinterpret_cast<const uint8_t*>(status.data()),
+        unit != nullptr ? steps.data() : nullptr, down.data(), up.data(), pivot_tolerance, out);
+    return MI_LP_OK;
+  });
+}
+
 int mi_lp_column_combinations(mi_lp* h, const double* x, int32_t k, double* out) {
   if (h == nullptr || x == nullptr || out == nullptr) return MI_LP_ERROR_NULL;
   if (!h->solved) return MI_LP_ERROR_STATE;

@@ -96,6 +96,41 @@ struct PanelSparseArgs {
   double* vals;
 };
 
+// The panel result reduced to one branching penalty record per vector
+// (panel_kernels.hip, penalties_tile / penalties_fold; include/mi_lp.h
+// mi_lp_row_penalties has the rule). alpha = in[col * K + v]; d, status and
+// unit are per column, dist per vector. A column that takes part in a
+// direction adds one to its count and offers a candidate >= +0.0 (never NaN,
+// never -0.0); the record keeps the smallest candidate and the lowest column
+// attaining it. Partials are (minimum, column, count) per (vector, direction,
+// tile), at [(v * 2 + direction) * tiles + tile], direction 0 = down; without
+// a column they are (+inf, kNoPenaltyColumn, 0).
+struct BranchPenalty {  // mi_lp_branch_penalty of include/mi_lp.h
+  double down;
+  double up;
+  int32_t down_col;
+  int32_t up_col;
+  int32_t down_count;
+  int32_t up_count;
+};
+constexpr int kNoPenaltyColumn = 0x7fffffff;
+struct PenaltyArgs {
+  const double* in;       // interleaved panel result, ncols x K
+  int ncols;
+  int kp;                 // vectors in use (<= K)
+  int tiles;              // ceil(ncols / kPanelTileColumns)
+  const double* d;        // ncols: reduced costs, minimisation sense
+  const uint8_t* status;  // ncols: MI_LP_BASIC .. MI_LP_FREE
+  const double* unit;     // ncols: integer steps, or nullptr (all 0)
+  const double* down_dist;  // kp: the panel's vectors
+  const double* up_dist;    // kp
+  double pivot_tolerance;
+  double* tile_min;       // 2 kp x tiles
+  int32_t* tile_col;      // 2 kp x tiles
+  int* tile_count;        // 2 kp x tiles
+  BranchPenalty* out;     // kp
+};
+
 // Row sums of [A | I] against a panel of K points (panel_kernels.hip,
 // row_sums_panel). The points are column-interleaved, x[col * K + v], zero
 // for the padding points v >= kp; the results are row-interleaved,
@@ -666,6 +701,8 @@ hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, do
                               int64_t ld, hipStream_t s);
 // panel_count, panel_offsets and panel_write for one panel, in that order.
 hipError_t panel_sparse(int width, const milp_kernels::PanelSparseArgs& args, hipStream_t s);
+// penalties_tile, then penalties_fold (kp workgroups), on one stream.
+hipError_t panel_penalties(int width, const milp_kernels::PenaltyArgs& args, hipStream_t s);
 // Row sums for a panel of `width` (1, 4 or 16) points in one pass over the
 // rows of [A | I] (panel_kernels.hip row_sums_panel_kernel).
 hipError_t row_sums_panel(int width, const milp_kernels::RowPanelArgs& args, hipStream_t s);

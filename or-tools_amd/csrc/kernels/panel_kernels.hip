@@ -16,7 +16,9 @@
 // The sparse form (panel_count / panel_offsets / panel_write, at the end)
 // filters out[col * K + v] by a column mask and a drop tolerance and packs
 // the kept (column, value) pairs per vector in increasing column order; it
-// replaces deinterleave_kernel when the caller wants sparse rows.
+// replaces deinterleave_kernel when the caller wants sparse rows. The
+// branching penalties (penalties_tile / penalties_fold, after it) reduce
+// out[col * K + v] to one 32-byte record per vector instead.
 //
 // The other direction, row sums [A | I] x for a panel of K points
 // (row_sums_panel_kernel and the kernels that build its interleaved points:
@@ -381,6 +383,197 @@ __global__ __launch_bounds__(kPanelTileColumns) void panel_write_kernel(PanelSpa
         return panel_keep(x, panel_mask_bit(a.mask, col), a.drop_tolerance);
       },
       a.cols, a.vals, tile_vals);
+}
+
+// ---------------------------------------------------------------------------
+// Branching penalties out of the interleaved panel result (include/mi_lp.h
+// mi_lp_row_penalties has the rule), in two launches on one stream; they
+// replace deinterleave_kernel when the caller wants one record per vector.
+//   penalties_tile  panel_count_kernel's tile and thread layout: thread t
+//                   reads elements t, t + 256, ... and meets one vector only,
+//                   v = t % K, at columns t / K + j * (256 / K), ascending in
+//                   j. Per direction it keeps (minimum, column, count) in
+//                   registers; the lanes of a vector combine by shuffles, the
+//                   four waves through LDS: one partial per (vector,
+//                   direction, tile).
+//   penalties_fold  workgroup v folds vector v's partials into its record.
+// (minimum, column) partials merge to the smaller candidate and, among equal
+// candidates, the lower column. A candidate is >= +0.0 and never NaN, so the
+// merge is exact and symmetric: the result does not depend on the reduction
+// tree. Without a column a partial is (+inf, kNoPenaltyColumn): a +inf
+// candidate at a real column replaces it.
+__device__ __forceinline__ void penalty_merge(double* value, int* col, double other_value,
+                                              int other_col) {
+  if (other_value < *value || (other_value == *value && other_col < *col)) {
+    *value = other_value;
+    *col = other_col;
+  }
+}
+
+// One direction's candidate of an eligible column: dist * (cost / |alpha|),
+// at least cost * unit for an integer column, every operation rounded on its
+// own; a NaN (0 * inf, inf / inf) counts as +0.0.
+__device__ __forceinline__ double penalty_candidate(double cost, double abs_alpha, double dist,
+                                                    double unit) {
+  const double r = cost / abs_alpha;
+  double c = dist * r;
+  if (unit > 0.0) {
+    const double step = cost * unit;
+    c = c < step ? step : c;
+  }
+  return c != c ? 0.0 : c;
+}
+
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void penalties_tile_kernel(PenaltyArgs a) {
+  static_assert(kPanelTileColumns == 256 && kPanelTileColumns % K == 0 && kWave % K == 0,
+                "a thread owns one vector");
+  constexpr int kWaves = kPanelTileColumns / kWave;
+  __shared__ double wave_min[kWaves][2][K];
+  __shared__ int wave_col[kWaves][2][K];
+  __shared__ int wave_count[kWaves][2][K];
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int col0 = tile * kPanelTileColumns;
+  const int cols = min(kPanelTileColumns, a.ncols - col0);
+  const double* __restrict__ in = a.in + static_cast<int64_t>(col0) * K;
+  const int v = t % K;
+  double best[2] = {__builtin_inf(), __builtin_inf()};
+  int best_col[2] = {kNoPenaltyColumn, kNoPenaltyColumn};
+  int count[2] = {0, 0};
+  if (v < a.kp) {
+    const double dist[2] = {a.down_dist[v], a.up_dist[v]};
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int cl = t / K + j * (kPanelTileColumns / K);
+      if (cl < cols) {
+        const int col = col0 + cl;
+        const double alpha = in[t + j * kPanelTileColumns];
+        const int status = a.status[col];
+        if (status == 0 || status == 1) continue;  // MI_LP_BASIC, MI_LP_FIXED_VALUE
+        const double d = a.d[col];
+        const double unit = a.unit != nullptr ? a.unit[col] : 0.0;
+        const bool at_lower = status == 2;  // MI_LP_AT_LOWER_BOUND
+        const bool at_upper = status == 3;  // MI_LP_AT_UPPER_BOUND
+        const bool is_free = !at_lower && !at_upper;  // MI_LP_FREE
+        const double cost = at_lower ? (d > 0.0 ? d : 0.0) : (at_upper ? (d < 0.0 ? -d : 0.0) : 0.0);
+        bool eligible[2];
+        double candidate[2];
+        if (alpha != alpha || d != d) {
+          eligible[0] = eligible[1] = true;
+          candidate[0] = candidate[1] = 0.0;
+        } else {
+          const double abs_alpha = fabs(alpha);
+          if (!(abs_alpha > a.pivot_tolerance)) continue;
+          const bool positive = alpha > 0.0;
+          eligible[0] = is_free || (at_lower && positive) || (at_upper && !positive);
+          eligible[1] = is_free || (at_lower && !positive) || (at_upper && positive);
+#pragma unroll
+          for (int dir = 0; dir < 2; ++dir) {
+            candidate[dir] = penalty_candidate(cost, abs_alpha, dist[dir], unit);
+          }
+        }
+#pragma unroll
+        for (int dir = 0; dir < 2; ++dir) {
+          if (eligible[dir]) {
+            ++count[dir];
+            penalty_merge(&best[dir], &best_col[dir], candidate[dir], col);
+          }
+        }
+      }
+    }
+  }
+  // Lanes l, l + K, l + 2K, ... of a wave hold the same vector.
+#pragma unroll
+  for (int off = K; off < kWave; off <<= 1) {
+#pragma unroll
+    for (int dir = 0; dir < 2; ++dir) {
+      count[dir] += __shfl_xor(count[dir], off, kWave);
+      const double other = __shfl_xor(best[dir], off, kWave);
+      const int other_col = __shfl_xor(best_col[dir], off, kWave);
+      penalty_merge(&best[dir], &best_col[dir], other, other_col);
+    }
+  }
+  const int lane = t & (kWave - 1);
+  const int wave = t / kWave;
+  if (lane < K) {  // lane == v
+#pragma unroll
+    for (int dir = 0; dir < 2; ++dir) {
+      wave_min[wave][dir][lane] = best[dir];
+      wave_col[wave][dir][lane] = best_col[dir];
+      wave_count[wave][dir][lane] = count[dir];
+    }
+  }
+  __syncthreads();
+  if (t < 2 * K && t % K < a.kp) {  // thread (direction t / K, vector t % K)
+    const int dir = t / K;
+    double value = wave_min[0][dir][v];
+    int col = wave_col[0][dir][v];
+    int c = wave_count[0][dir][v];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) {
+      c += wave_count[w][dir][v];
+      penalty_merge(&value, &col, wave_min[w][dir][v], wave_col[w][dir][v]);
+    }
+    const int64_t at = static_cast<int64_t>(v * 2 + dir) * a.tiles + tile;
+    a.tile_min[at] = value;
+    a.tile_col[at] = col;
+    a.tile_count[at] = c;
+  }
+}
+
+// Workgroup v folds vector v's tile partials of both directions into its
+// record: the smallest candidate, the lowest column attaining it (-1 without
+// one) and the integer sum of the counts (at most ncols < 2^31).
+__global__ __launch_bounds__(kPanelOffsetsStep) void penalties_fold_kernel(PenaltyArgs a) {
+  constexpr int kWaves = kPanelOffsetsStep / kWave;
+  __shared__ double wave_min[kWaves][2];
+  __shared__ int wave_col[kWaves][2];
+  __shared__ int wave_count[kWaves][2];
+  const int t = threadIdx.x;
+  const int v = blockIdx.x;  // < kp: the grid is exactly kp workgroups
+  double best[2] = {__builtin_inf(), __builtin_inf()};
+  int best_col[2] = {kNoPenaltyColumn, kNoPenaltyColumn};
+  int count[2] = {0, 0};
+#pragma unroll
+  for (int dir = 0; dir < 2; ++dir) {
+    const int64_t base = static_cast<int64_t>(v * 2 + dir) * a.tiles;
+    for (int tile = t; tile < a.tiles; tile += kPanelOffsetsStep) {
+      count[dir] += a.tile_count[base + tile];
+      penalty_merge(&best[dir], &best_col[dir], a.tile_min[base + tile], a.tile_col[base + tile]);
+    }
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+      count[dir] += __shfl_xor(count[dir], off, kWave);
+      const double other = __shfl_xor(best[dir], off, kWave);
+      const int other_col = __shfl_xor(best_col[dir], off, kWave);
+      penalty_merge(&best[dir], &best_col[dir], other, other_col);
+    }
+    if ((t & (kWave - 1)) == 0) {
+      wave_min[t / kWave][dir] = best[dir];
+      wave_col[t / kWave][dir] = best_col[dir];
+      wave_count[t / kWave][dir] = count[dir];
+    }
+  }
+  __syncthreads();
+  if (t == 0) {
+#pragma unroll
+    for (int dir = 0; dir < 2; ++dir) {
+#pragma unroll
+      for (int w = 1; w < kWaves; ++w) {
+        count[dir] += wave_count[w][dir];
+        penalty_merge(&best[dir], &best_col[dir], wave_min[w][dir], wave_col[w][dir]);
+      }
+    }
+    BranchPenalty r;
+    r.down = best[0];
+    r.up = best[1];
+    r.down_col = best_col[0] == kNoPenaltyColumn ? -1 : best_col[0];
+    r.up_col = best_col[1] == kNoPenaltyColumn ? -1 : best_col[1];
+    r.down_count = count[0];
+    r.up_count = count[1];
+    a.out[v] = r;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1127,6 +1320,16 @@ hipError_t panel_sparse(int width, const PanelSparseArgs& args, hipStream_t s) {
     panel_count_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
     panel_offsets_kernel<<<1, kPanelOffsetsStep, 0, s>>>(args);
     panel_write_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+  });
+}
+
+hipError_t panel_penalties(int width, const PenaltyArgs& args, hipStream_t s) {
+  if (args.ncols <= 0 || args.kp <= 0) return hipSuccess;
+  if (args.tiles != panel_div_up(args.ncols, kPanelTileColumns)) return hipErrorInvalidValue;
+  return for_panel_width(width, [&](auto w) {
+    constexpr int K = decltype(w)::value;
+    penalties_tile_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+    penalties_fold_kernel<<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
   });
 }
 

@@ -388,6 +388,48 @@ def branch_overrides(trail, x, cols):
     return base_lb, base_ub, overrides
 
 
+PENALTY_PIVOT_TOLERANCE = 1e-9  # Glop's ratio_test_zero_threshold (parameters.proto)
+
+
+def branch_penalties(constraint, trail, x, cols, pivot_tolerance=PENALTY_PIVOT_TOLERANCE):
+    """Lower bounds on the objective of the children of a solved node before
+    any of them is solved: the Driebeek-Tomlin penalties of the first dual
+    pivot (handle.branching_penalties, include/mi_lp.h
+    mi_lp_branching_penalties), one call for all of `cols` (fractional, hence
+    BASIC, columns of the node's LP solution x at CP scale).
+
+    The distances to floor(x) and ceil(x) go in at the LP's scale (times
+    VariableScalingFactor, as scale_bounds does with the bounds) and the
+    integer columns' step is one CP unit, their factor. A penalty is in the
+    simplex's objective units; times the LP's obj_scale it is at the scale of
+    the objective value (the inverse of reduced_cost_deductions' lp_delta).
+
+    Returns one dict per child in branch_lps order (down, then up, per
+    column): "bound", the child's objective lower bound (+inf when infeasible);
+    "infeasible", no column can make the first pivot; "cutoff", the child
+    cannot beat the incumbent: infeasible, or ceil(bound - kCpEpsilon) exceeds
+    trail.obj_ub (what enqueue_obj_ge would call a conflict)."""
+    if constraint.lp.maximize:
+        raise ValueError("branch_penalties: CP-SAT's LPs are minimised")
+    cols = [int(c) for c in cols]
+    factor = constraint.factor
+    values = np.array([float(x[c]) for c in cols])
+    down = (values - np.floor(values)) * factor[cols]
+    up = (np.ceil(values) - values) * factor[cols]
+    unit = np.zeros(constraint.lp.n)
+    unit[constraint.int_cols] = factor[constraint.int_cols]
+    records = constraint.h.branching_penalties(cols, down, up, unit, pivot_tolerance)
+    obj_scale = constraint.lp_data.obj_scale
+    out = []
+    for rec in records:
+        for penalty, count in ((rec["down"], rec["down_count"]), (rec["up"], rec["up_count"])):
+            infeasible = int(count) == 0
+            bound = math.inf if infeasible else constraint.lp_objective + float(penalty) * obj_scale
+            cutoff = bound == math.inf or math.ceil(bound - K_CP_EPSILON) > trail.obj_ub
+            out.append({"bound": bound, "infeasible": infeasible, "cutoff": cutoff})
+    return out
+
+
 def tightened_overrides(result):
     """LpHandle.tightened_columns(_from)'s result (col_starts, cols, new_lbs,
     new_ubs, summaries) as overrides[j] = (cols, new_lbs, new_ubs), one per

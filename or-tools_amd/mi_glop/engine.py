@@ -32,6 +32,11 @@ SIMPLEX_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, cty
 POINT_VIOLATIONS = np.dtype([("count", np.int64), ("worst", np.float64),
                              ("worst_row", np.int32), ("reserved", np.int32)])
 assert POINT_VIOLATIONS.itemsize == 24
+# include/mi_lp.h mi_lp_branch_penalty: one record per tableau row.
+BRANCH_PENALTY = np.dtype([("down", np.float64), ("up", np.float64), ("down_col", np.int32),
+                           ("up_col", np.int32), ("down_count", np.int32),
+                           ("up_count", np.int32)])
+assert BRANCH_PENALTY.itemsize == 32
 # mi_lp_propagation (include/mi_lp.h) as a numpy record.
 PROPAGATION = np.dtype([("status", np.int32), ("rounds", np.int32), ("moves", np.int64),
                         ("worst", np.float64), ("worst_col", np.int32), ("kept", np.int32)])
@@ -130,6 +135,10 @@ def lib():
     L.mi_lp_get_tableau_rows_sparse.argtypes = [vp, vp, ctypes.c_int32, ctypes.c_double,
                                                 ctypes.c_uint32, vp, vp]
     L.mi_lp_get_sparse_rows.argtypes = [vp, vp, vp]
+    L.mi_lp_row_penalties.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp,
+                                      ctypes.c_double, vp]
+    L.mi_lp_branching_penalties.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, ctypes.c_double,
+                                            vp, vp]
     L.mi_lp_column_combinations.argtypes = [vp, vp, ctypes.c_int32, vp]
     L.mi_lp_column_combinations_from.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp]
     L.mi_lp_column_combinations_violations.argtypes = [vp, vp, ctypes.c_int32, vp, vp,
@@ -611,6 +620,72 @@ class LpHandle:
                    None if left is None else _p(left))
         out = self._sparse_rows(starts, k)
         return out + (left[:k],) if with_left_inverses else out
+
+    def row_penalties(self, Y, d, status, down_dist, up_dist, unit=None, pivot_tolerance=0.0):
+        """One branching penalty record (BRANCH_PENALTY: down, up, down_col,
+        up_col, down_count, up_count) per row of row_combinations(Y), reduced
+        on the GPU (include/mi_lp.h mi_lp_row_penalties has the rule). d,
+        status and unit cover the n+m columns, the distances the k vectors;
+        unit None means all 0."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[None, :]
+        total = self.lp.n + self.lp.m
+        if Y.ndim != 2 or Y.shape[1] != self.lp.m:
+            raise ValueError(f"Y must be (k, {self.lp.m}), got {Y.shape}")
+        k = Y.shape[0]
+        d = np.ascontiguousarray(d, dtype=np.float64)
+        status = np.ascontiguousarray(status, dtype=np.int8)
+        down = np.ascontiguousarray(down_dist, dtype=np.float64).reshape(-1)
+        up = np.ascontiguousarray(up_dist, dtype=np.float64).reshape(-1)
+        if unit is not None:
+            unit = np.ascontiguousarray(unit, dtype=np.float64)
+        if d.shape != (total,) or status.shape != (total,) or \
+                (unit is not None and unit.shape != (total,)):
+            raise ValueError(f"d, status and unit must have {total} entries")
+        if len(down) != k or len(up) != k:
+            raise ValueError(f"the distances must have {k} entries")
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            Y = np.zeros((1, self.lp.m), np.float64)
+            down = up = np.zeros(1, np.float64)
+        out = np.zeros(max(k, 1), BRANCH_PENALTY)
+        self._call("row_penalties", _p(Y), k, _p(d), _p(status),
+                   None if unit is None else _p(unit), _p(down), _p(up),
+                   ctypes.c_double(pivot_tolerance), _p(out))
+        return out[:k]
+
+    def branching_penalties(self, cols, down_dist=None, up_dist=None, unit=None,
+                            pivot_tolerance=0.0, with_left_inverses=False):
+        """The records of the k BASIC columns `cols` of the current basis
+        (include/mi_lp.h mi_lp_branching_penalties): tableau rows, statuses and
+        reduced costs are the solver's. Distances None: the fractional parts of
+        the columns' values. unit: n entries, or None. With with_left_inverses
+        also returns the (k, m) left inverses."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        k = len(cols)
+        dists = []
+        for dist in (down_dist, up_dist):
+            if dist is not None:
+                dist = np.ascontiguousarray(dist, dtype=np.float64).reshape(-1)
+                if len(dist) != k:
+                    raise ValueError(f"the distances must have {k} entries")
+                if k == 0:
+                    dist = np.zeros(1, np.float64)
+            dists.append(dist)
+        if unit is not None:
+            unit = np.ascontiguousarray(unit, dtype=np.float64)
+            if unit.shape != (self.lp.n,):
+                raise ValueError(f"unit must have {self.lp.n} entries")
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            cols = np.zeros(1, np.int32)
+        out = np.zeros(max(k, 1), BRANCH_PENALTY)
+        left = np.zeros((max(k, 1), self.lp.m), np.float64) if with_left_inverses else None
+        self._call("branching_penalties", _p(cols), k,
+                   None if dists[0] is None else _p(dists[0]),
+                   None if dists[1] is None else _p(dists[1]),
+                   None if unit is None else _p(unit), ctypes.c_double(pivot_tolerance),
+                   _p(out), None if left is None else _p(left))
+        return (out[:k], left[:k]) if with_left_inverses else out[:k]
 
     def _points(self, X, what):
         """X as a contiguous (k, n+m) array: (k, n) gets zero slacks appended,
