@@ -417,6 +417,111 @@ int mi_lp_branching_penalties(mi_lp* h, const int32_t* cols, int32_t k, const do
                               const double* up_dist, const double* unit, double pivot_tolerance,
                               mi_lp_branch_penalty* out, double* left_inverses);
 
+/* The same rows turned on the GPU into Gomory mixed-integer cuts in the space
+ * of the structural columns: the GMI formula per column, the slacks eliminated
+ * by a second pass over A, and only the kept coefficients of the finished cut
+ * (and one 32-byte summary per cut) brought down. Glop's dictionary is
+ * [A | I] x = 0; with alpha = rho^T [A | I] for row r of B^-1, row r reads
+ * x_B(r) + sum over non-basic j of alpha_j x_j = 0.
+ *   mi_lp_row_gomory_cuts   per vector v < k the caller gives f0[v], the
+ *                           fractional part of the basic variable in integer
+ *                           units, strictly inside (0, 1), and row_unit[v], the
+ *                           integer step of the basic column in LP units, finite
+ *                           and > 0 (unscaled: 1.0); per column status (n+m,
+ *                           MI_LP_BASIC .. MI_LP_FREE) and unit (n+m, 0 for a
+ *                           continuous column; NULL: all 0; the meaning is that
+ *                           of mi_lp_row_penalties' unit). For every column col
+ *                           of [A | I], alpha is bit for bit
+ *                           mi_lp_row_combinations' out[v (n+m) + col]. The
+ *                           coefficient g, in doubles without FMA:
+ *                           1. BASIC and FIXED_VALUE columns: g = +0.0.
+ *                           2. A NaN alpha: g = +0.0, counted in bad_count.
+ *                           3. Else, unless fabs(alpha) > zero_tolerance
+ *                              (strict): g = +0.0.
+ *                           4. Else a FREE column: g = +0.0, counted in
+ *                              bad_count (a cut with a free non-basic column in
+ *                              its support is not valid: the caller drops it).
+ *                           5. Else abar = alpha AT_LOWER_BOUND, -alpha
+ *                              AT_UPPER_BOUND, and with u = unit[col]:
+ *                              u > 0:  t = (abar * u) / row_unit[v];
+ *                                      f = t - floor(t);
+ *                                      gamma = f <= f0 ? f / f0
+ *                                                      : (1.0 - f) / (1.0 - f0);
+ *                                      gamma = gamma / u;
+ *                              u == 0: t = abar / row_unit[v];
+ *                                      gamma = t > 0 ? t / f0
+ *                                                    : (-t) / (1.0 - f0).
+ *                           6. g = gamma AT_LOWER_BOUND, 0.0 - gamma
+ *                              AT_UPPER_BOUND.
+ *                           Slack elimination: the slack of row r is
+ *                           s_r = -(A x)_r, so with y'[r] = g[n + r] and s = bit
+ *                           for bit mi_lp_row_combinations(y')'s value at
+ *                           col < n, the cut coefficient is c = g[col] - s, one
+ *                           rounded subtraction. Column col is kept iff
+ *                           fabs(c) > drop_tolerance (strict, as in the sparse
+ *                           rows: +-0.0 is dropped, +-inf kept); a NaN c is
+ *                           dropped and counted in bad_count. The cut is
+ *                           sum c_j x_j >= rhs over the structural columns. rhs
+ *                           is NOT computed (a floating-point sum over the
+ *                           columns would fix a summation order): at the node's
+ *                           LP point x* every non-basic column sits on its
+ *                           bound, so in exact arithmetic
+ *                           rhs = 1 + sum_j c_j x*_j, which the caller forms
+ *                           from the list it downloads (the Python helper uses
+ *                           math.fsum, which does not depend on the order).
+ *                           row_starts: k + 1 entries; per vector the kept
+ *                           structural columns in strictly increasing order,
+ *                           each with c's bits. summaries: one per vector (below;
+ *                           an integer sum, exact extrema and lowest indices:
+ *                           the same bits in any reduction order). A NULL
+ *                           row_starts asks for the summaries alone: no list is
+ *                           built, downloaded or stored, and a stored list
+ *                           stays. summaries may be NULL; both NULL is
+ *                           MI_LP_ERROR_NULL. Everything is the caller's; changes
+ *                           no solve state.
+ *   mi_lp_gomory_cuts       the same for the k BASIC structural columns cols of
+ *                           the current basis: y_j, the side effects and
+ *                           left_inverses (k x m, or NULL) are those of
+ *                           mi_lp_get_tableau_rows for the rows of cols; status
+ *                           = mi_lp_get_state's; unit: n entries, required
+ *                           (slacks get 0); row_unit[j] = unit[cols[j]];
+ *                           f0[j] = t - floor(t) with t = value / unit[cols[j]],
+ *                           value = mi_lp_get_primal[cols[j]].
+ *   mi_lp_get_cut_rows      copies the stored lists out (row_starts[k] entries
+ *                           each): a sixth store of the handle, apart from the
+ *                           others; it lives until the next cut call that builds
+ *                           lists, mi_lp_load or mi_lp_destroy.
+ * MI_LP_ERROR_NULL: NULL h, y, status, f0, row_unit, cols, unit
+ * (mi_lp_gomory_cuts), or row_starts and summaries both NULL. Before a solve:
+ * MI_LP_ERROR_STATE; mi_lp_get_cut_rows before any list-building call or after
+ * mi_lp_load: MI_LP_ERROR_STATE. MI_LP_ERROR_INVALID_PROBLEM: k < 0, a status
+ * outside 0..4, a tolerance that is negative or NaN, an infinite
+ * zero_tolerance, a unit that is negative, NaN or infinite, a row_unit that is
+ * not finite and > 0, an f0 (given or computed) outside the open interval
+ * (0, 1), a column of cols outside [0, n), not BASIC or with unit 0. On every
+ * error nothing is written and the store is untouched. k = 0 succeeds, writes
+ * row_starts[0] = 0 and stores an empty result.
+ * With column shards (MILP_SHARDS) both compute calls return
+ * MI_LP_ERROR_STATE ("not with column shards") before any device work: the
+ * slack part of g would have to be joined across the shards between the two
+ * passes, and that join is not built. */
+typedef struct mi_lp_cut_summary {
+  double max_abs;    /* largest fabs(c) among the kept entries, 0.0 without one */
+  double min_abs;    /* smallest, +inf without one */
+  int32_t count;     /* kept entries */
+  int32_t bad_count; /* columns of steps 2 and 4 over all n+m columns, plus the NaN c's */
+  int32_t max_col;   /* lowest column attaining max_abs, -1 without one */
+  int32_t min_col;
+} mi_lp_cut_summary;
+int mi_lp_row_gomory_cuts(mi_lp* h, const double* y, int32_t k, const int8_t* status,
+                          const double* unit, const double* f0, const double* row_unit,
+                          double zero_tolerance, double drop_tolerance,
+                          int64_t* row_starts, mi_lp_cut_summary* summaries);
+int mi_lp_gomory_cuts(mi_lp* h, const int32_t* cols, int32_t k, const double* unit,
+                      double zero_tolerance, double drop_tolerance, int64_t* row_starts,
+                      mi_lp_cut_summary* summaries, double* left_inverses);
+int mi_lp_get_cut_rows(const mi_lp* h, int32_t* cols, double* vals);
+
 /* The other half: the row sums [A | I] x_j of k candidate points in one call
  * that reads A once per panel of up to 16 points (what a caller reads cut
  * violations and row feasibility of roundings, neighbours or ray combinations

@@ -103,6 +103,30 @@ typedef struct mi_devop_penalties {
   int64_t bytes_down; /* device-to-host bytes of the call */
 } mi_devop_penalties;
 
+/* mi_lp_cut_summary of include/mi_lp.h, restated so that this header stands
+ * alone. */
+typedef struct mi_devop_cut_summary {
+  double max_abs;
+  double min_abs;
+  int32_t count;
+  int32_t bad_count;
+  int32_t max_col; /* -1 when count == 0 */
+  int32_t min_col;
+} mi_devop_cut_summary;
+/* DeviceLp::LastCuts: the last column_cuts_panel. */
+typedef struct mi_devop_cuts {
+  int32_t sparse; /* as mi_devop_panel */
+  int32_t dense;
+  int32_t panels;
+  int32_t width;
+  int32_t tiles;            /* tiles of tile_columns columns over all N columns */
+  int32_t structural_tiles; /* over the n structural columns */
+  int32_t lists;            /* lists were built */
+  int32_t reserved;
+  int64_t kept;       /* entries of all cuts */
+  int64_t bytes_down; /* device-to-host bytes of the call */
+} mi_devop_cuts;
+
 /* DeviceLp::LastColumnDots: the last launch of the column-dot kernels. */
 typedef struct mi_devop_column_dots {
   int32_t mode;         /* DotMode of simplex_kernels.hip: 1 pricing, 5 pricing with dots */
@@ -394,6 +418,20 @@ typedef struct mi_devop_api {
                                 const double* down_dist, const double* up_dist,
                                 double pivot_tolerance, mi_devop_branch_penalty* out);
   int (*last_penalties)(mi_devop* h, mi_devop_penalties* out);
+  /* Appended after last_penalties. DeviceLp::ColumnCutsPanel (the rule:
+   * include/mi_lp.h mi_lp_row_gomory_cuts). y: k x m; status: N; unit: N, or
+   * NULL; f0, row_unit: k. row_starts: k + 1, or NULL (summaries alone: cols
+   * and vals are not touched); cols, vals: capacity entries; summaries: k, or
+   * NULL. A result of more than `capacity` entries returns MI_DEVOP_CAPACITY
+   * with nothing written. The arguments are checked here as
+   * mi_lp_row_gomory_cuts checks them: a bad one is an error with nothing
+   * written and no device error. */
+  int (*column_cuts_panel)(mi_devop* h, const double* y, int k, const int8_t* status,
+                           const double* unit, const double* f0, const double* row_unit,
+                           double zero_tolerance, double drop_tolerance, int64_t* row_starts,
+                           int32_t* cols, double* vals, int64_t capacity,
+                           mi_devop_cut_summary* summaries);
+  int (*last_cuts)(mi_devop* h, mi_devop_cuts* out);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

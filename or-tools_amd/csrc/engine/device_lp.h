@@ -238,6 +238,48 @@ class DeviceLp : public DeviceSolver {
   };
   LastPenalties last_penalties() const;
 
+  // The same dots turned into Gomory mixed-integer cuts over the n structural
+  // columns (include/mi_lp.h mi_lp_row_gomory_cuts has the rule). Per panel,
+  // on one stream: the dot launches of ColumnDotsPanel (alpha);
+  // gomory_transform_tile (g: the structural part into a buffer of its own,
+  // the slack part into the interleaved vectors, which rho has left); the
+  // dot launches again (s = g_slack^T A); gomory_combine_tile (c = g - s in
+  // place, summary partials) and gomory_fold; with lists, panel_count /
+  // panel_offsets / panel_write over the n structural columns without a mask.
+  // Only the kp summaries, the kp totals and the kept (4-byte column, 8-byte
+  // value) entries come down: no transfer grows with N. status, unit, f0 and
+  // row_unit go up once per call. lists == false: no count, offsets or write
+  // pass (out's list members stay empty). Not with column shards (the slack
+  // part of g would have to be joined across the shards between the passes):
+  // a DeviceError. Nothing a solve reads is written. Synchronizes before it
+  // returns.
+  struct CutRows {
+    std::vector<int64_t> row_starts;  // k + 1 (lists)
+    std::vector<int32_t> cols;        // row_starts[k]
+    std::vector<double> vals;
+    std::vector<mi_lp_cut_summary> summaries;  // k
+  };
+  void ColumnCutsPanel(const double* y, int k, const uint8_t* status, const double* unit,
+                       const double* f0, const double* row_unit, double zero_tolerance,
+                       double drop_tolerance, bool lists, CutRows* out);
+  // Preconditions: k >= 0, every status in 0..4, both tolerances >= 0 (not
+  // NaN), zero_tolerance finite, every unit finite and >= 0 (unit may be
+  // null), every row_unit finite and > 0, every f0 inside (0, 1).
+  static bool ValidCutArgs(int num_cols, int k, const int8_t* status, const double* unit,
+                           const double* f0, const double* row_unit, double zero_tolerance,
+                           double drop_tolerance);
+  // The last ColumnCutsPanel (test record); last_panel() and
+  // last_panel_sparse() are not changed by it.
+  struct LastCuts {
+    LastPanel panel;
+    int tiles = 0;            // tiles of kPanelTileColumns columns over all N columns
+    int structural_tiles = 0; // over the n structural columns
+    bool lists = false;       // lists were built
+    int64_t kept = 0;         // entries of all cuts
+    int64_t bytes_down = 0;   // device-to-host bytes of the call
+  };
+  LastCuts last_cuts() const;
+
   // --- 1 + ||a_j||^2 for relevant j (identity basis) -------------------
   void ColumnSquaredNorms(std::vector<double>* out);
 

@@ -1,6 +1,6 @@
 // The workspace of DeviceLp's panel calls (device_panel.hip): the buffers of
-// ColumnDotsPanel, ColumnDotsPanelSparse, ColumnPenaltiesPanel, RowSumsPanel,
-// RowSumsPanelFrom,
+// ColumnDotsPanel, ColumnDotsPanelSparse, ColumnPenaltiesPanel,
+// ColumnCutsPanel, RowSumsPanel, RowSumsPanelFrom,
 // RowViolationsPanel(From), BoundRangesPanel(From),
 // BoundInfeasiblePanel(From), BoundImpliedPanel(From),
 // BoundTightenedPanel(From), BoundPropagatePanel(From) and
@@ -85,6 +85,9 @@ struct PanelWorkspace {
   //   flat: vector-major, kp N        the results on their way      the points on their way
   //                                   down (sparse form: the        up, then the results
   //                                   packed kept values)           (kp m) on their way down
+  // The Gomory cuts (ColumnCutsPanel) are column dots twice over: `rows`
+  // holds rho, then the slack part of g; `cols` alpha, then s, then the cut
+  // coefficients c over its first n columns (see cut_g below).
   // The row violations (RowViolationsPanel, RowViolationsPanelFrom) are row
   // sums up to the results in `rows`; then `flat` takes the packed kept
   // activities (at most kp m <= kp N), the points having left it.
@@ -154,6 +157,25 @@ struct PanelWorkspace {
   DeviceBuffer<milp_kernels::BranchPenalty> penalties;       // kPanelMaxWidth
   PinnedBuffer<milp_kernels::BranchPenalty> penalties_host;  // kPanelMaxWidth
 
+  // ColumnCutsPanel only: column dots up to the results (alpha) in `cols`.
+  // gomory_transform_tile writes g of the structural columns into `cut_g` and
+  // g of slack column n + r over rho in `rows` (row-interleaved: the vector
+  // y' of the second dot pass, zero in the padding slots); the dot kernels
+  // run again and leave s in `cols`; gomory_combine_tile writes c = g - s
+  // over the first n columns of `cols` in place, where the sparse form's
+  // passes then read it as a panel result of n columns (`flat` takes the
+  // packed kept values, kept_cols / counts / offsets / totals as for the
+  // sparse rows). The per-tile partials: tile_worst takes the largest and
+  // then the smallest fabs(c) (2 kp x structural tiles), tile_worst_row the
+  // columns attaining them likewise, cut_counts the bad columns (kp x tiles
+  // over N), then the kept and the NaN counts (kp x structural tiles each).
+  // penalty_status and penalty_unit take the statuses and steps.
+  DeviceBuffer<double> cut_g;       // max(1, n) width, column-interleaved
+  DeviceBuffer<double> cut_vector;  // f0 (k), then row_unit (k), once per call
+  DeviceBuffer<int> cut_counts;
+  DeviceBuffer<milp_kernels::CutSummary> cut_summaries;       // kPanelMaxWidth
+  PinnedBuffer<milp_kernels::CutSummary> cut_summaries_host;  // kPanelMaxWidth
+
   // RowSumsPanelFrom and RowViolationsPanelFrom, uploaded once per call.
   DeviceBuffer<double> base;        // the base point, N
   DeviceBuffer<int64_t> ov_starts;  // k + 1
@@ -172,6 +194,7 @@ struct PanelWorkspace {
   DeviceLp::LastPanel last_panel;
   DeviceLp::LastPanelSparse last_panel_sparse;
   DeviceLp::LastPenalties last_penalties;
+  DeviceLp::LastCuts last_cuts;
   DeviceLp::LastRowPanel last_row_panel;
   DeviceLp::LastRowViolations last_row_violations;
   DeviceLp::LastBoundRanges last_bound_ranges;

@@ -1,6 +1,7 @@
 // DeviceLp's panel calls: k vectors per pass over [A | I] (see device_lp.h).
-// Column dots (ColumnDotsPanel, ColumnDotsPanelSparse, and their reduction to
-// branching penalties, ColumnPenaltiesPanel), row sums (RowSumsPanel,
+// Column dots (ColumnDotsPanel, ColumnDotsPanelSparse, their reduction to
+// branching penalties, ColumnPenaltiesPanel, and the Gomory cuts built from
+// two passes of them, ColumnCutsPanel), row sums (RowSumsPanel,
 // RowSumsPanelFrom), their violated rows (RowViolationsPanel,
 // RowViolationsPanelFrom) and the activity ranges of bound sets
 // (BoundRangesPanel(From), BoundInfeasiblePanel(From)) with the implied column
@@ -371,6 +372,161 @@ void DeviceLp::ColumnPenaltiesPanel(const double* y, int k, const double* d,
     w.last_penalties.bytes_down += int64_t(kp) * 32;
   });
   DeviceOp("column penalties panel done");
+}
+
+static_assert(sizeof(milp_kernels::CutSummary) == sizeof(mi_lp_cut_summary) &&
+                  sizeof(mi_lp_cut_summary) == 32 &&
+                  offsetof(milp_kernels::CutSummary, min_abs) ==
+                      offsetof(mi_lp_cut_summary, min_abs) &&
+                  offsetof(milp_kernels::CutSummary, count) == offsetof(mi_lp_cut_summary, count) &&
+                  offsetof(milp_kernels::CutSummary, bad_count) ==
+                      offsetof(mi_lp_cut_summary, bad_count) &&
+                  offsetof(milp_kernels::CutSummary, min_col) ==
+                      offsetof(mi_lp_cut_summary, min_col),
+              "kernel_args.h restates mi_lp_cut_summary");
+
+DeviceLp::LastCuts DeviceLp::last_cuts() const { return panel_->last_cuts; }
+
+bool DeviceLp::ValidCutArgs(int num_cols, int k, const int8_t* status, const double* unit,
+                            const double* f0, const double* row_unit, double zero_tolerance,
+                            double drop_tolerance) {
+  if (k < 0 || !(zero_tolerance >= 0.0) || !(zero_tolerance < HUGE_VAL) ||
+      !(drop_tolerance >= 0.0)) {
+    return false;
+  }
+  for (int j = 0; j < k; ++j) {  // every comparison is false for a NaN
+    if (!(f0[j] > 0.0 && f0[j] < 1.0)) return false;
+    if (!(row_unit[j] > 0.0 && row_unit[j] < HUGE_VAL)) return false;
+  }
+  for (int c = 0; c < num_cols; ++c) {
+    if (status[c] < MI_LP_BASIC || status[c] > MI_LP_FREE) return false;
+    if (unit != nullptr && !(unit[c] >= 0.0 && unit[c] < HUGE_VAL)) return false;
+  }
+  return true;
+}
+
+void DeviceLp::ColumnCutsPanel(const double* y, int k, const uint8_t* status, const double* unit,
+                               const double* f0, const double* row_unit, double zero_tolerance,
+                               double drop_tolerance, bool lists, CutRows* out) {
+  if (!shards_.empty()) throw DeviceError("column cuts panel: not with column shards");
+  PanelWorkspace& w = *panel_;
+  w.last_cuts = LastCuts();
+  w.last_cuts.lists = lists;
+  out->row_starts.clear();
+  if (lists) out->row_starts.assign(size_t(std::max(k, 0)) + 1, 0);
+  out->cols.clear();
+  out->vals.clear();
+  out->summaries.assign(size_t(std::max(k, 0)), mi_lp_cut_summary{0.0, HUGE_VAL, 0, 0, -1, -1});
+  if (k <= 0 || n_total_ <= 0) return;
+  DeviceOp("column cuts panel");
+  const PanelPlan plan = PanelKernelChoice();
+  const int n = n_total_ - m_;
+  const int tiles = (n_total_ + milp_kernels::kPanelTileColumns - 1) /
+                    milp_kernels::kPanelTileColumns;
+  const int tiles_n = (n + milp_kernels::kPanelTileColumns - 1) / milp_kernels::kPanelTileColumns;
+  const size_t N = size_t(n_total_);
+  Upload(w.penalty_status.Reserve(N, "panel statuses"), status, N);
+  if (unit != nullptr) {
+    Upload(w.penalty_unit.Reserve(N, "panel integer steps"), unit, N * sizeof(double));
+  }
+  double* per_vector = w.cut_vector.Reserve(2 * size_t(k), "panel cut vectors");
+  Upload(per_vector, f0, size_t(k) * sizeof(double));
+  Upload(per_vector + k, row_unit, size_t(k) * sizeof(double));
+  w.last_cuts.tiles = tiles;
+  w.last_cuts.structural_tiles = tiles_n;
+  ForEachPanel(k, [&](int first, int kp, int width) {
+    PanelUploadVectors(y, first, kp, width);
+    PanelTimer timer(&w, S(stream_));
+    PanelLaunchDots(plan, kp, width);
+    const size_t part_n = size_t(kp) * tiles_n;
+    milp_kernels::GomoryArgs a{};
+    a.cols = w.cols.get();
+    a.g = w.cut_g.Reserve(std::max<size_t>(1, size_t(n)) * width, "panel cut coefficients");
+    a.slack = w.rows.get();
+    a.ncols = n_total_;
+    a.n = n;
+    a.kp = kp;
+    a.tiles = tiles;
+    a.tiles_n = tiles_n;
+    a.status = w.penalty_status.get();
+    a.unit = unit != nullptr ? w.penalty_unit.get() : nullptr;
+    a.f0 = per_vector + first;
+    a.row_unit = per_vector + k + first;
+    a.zero_tolerance = zero_tolerance;
+    a.drop_tolerance = drop_tolerance;
+    a.tile_bad = w.cut_counts.Reserve(size_t(kp) * tiles + 2 * part_n, "panel cut counts");
+    a.tile_count = a.tile_bad + size_t(kp) * tiles;
+    a.tile_nan = a.tile_count + part_n;
+    a.tile_max = w.tile_worst.Reserve(std::max<size_t>(1, 2 * part_n), "panel tile extrema");
+    a.tile_min = a.tile_max + part_n;
+    a.tile_max_col =
+        w.tile_worst_row.Reserve(std::max<size_t>(1, 2 * part_n), "panel tile columns");
+    a.tile_min_col = a.tile_max_col + part_n;
+    a.out = w.cut_summaries.Reserve(milp_kernels::kPanelMaxWidth, "panel cut summaries");
+    const milp_kernels::CutSummary* host =
+        w.cut_summaries_host.Reserve(milp_kernels::kPanelMaxWidth, "panel cut summaries");
+    Check(milp_launch::panel_gomory_transform(width, a, S(stream_)), "panel cut transform");
+    PanelLaunchDots(plan, kp, width);  // y' = the slack part of g, in `rows`
+    Check(milp_launch::panel_gomory_combine(width, a, S(stream_)), "panel cut combine");
+    milp_kernels::PanelSparseArgs sp{};
+    const int64_t* totals = nullptr;
+    const bool pack = lists && n > 0;
+    if (pack) {
+      // The sparse form over the first n columns of `cols`; `flat` takes the
+      // packed values.
+      w.kept_cols.Reserve(size_t(n) * kp, "panel kept columns");
+      w.counts.Reserve(part_n, "panel counts");
+      w.offsets.Reserve(part_n + milp_kernels::kPanelMaxWidth, "panel offsets");
+      totals = w.totals.Reserve(milp_kernels::kPanelMaxWidth, "panel totals");
+      sp.in = w.cols.get();
+      sp.ncols = n;
+      sp.kp = kp;
+      sp.tiles = tiles_n;
+      sp.mask = nullptr;
+      sp.drop_tolerance = drop_tolerance;
+      sp.counts = w.counts.get();
+      sp.offsets = w.offsets.get();
+      sp.totals = w.offsets.get() + part_n;
+      sp.cols = w.kept_cols.get();
+      sp.vals = w.flat.get();
+      Check(milp_launch::panel_sparse(width, sp, S(stream_)), "panel cut rows");
+    }
+    timer.Launched();
+    if (pack) {
+      Check(hipMemcpyAsync(w.totals.get(), sp.totals, size_t(kp) * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+    }
+    Download(w.cut_summaries_host.get(), a.out, size_t(kp) * sizeof(*a.out));
+    int64_t kept = 0;
+    for (int v = 0; v < kp; ++v) {
+      const milp_kernels::CutSummary& s = host[v];
+      if (s.count < 0 || s.count > n || s.bad_count < 0 || s.max_col < -1 || s.max_col >= n ||
+          s.min_col < -1 || s.min_col >= n || (pack && totals[v] != s.count)) {
+        throw DeviceError("column cuts panel: bad summary");
+      }
+      out->summaries[first + v] =
+          mi_lp_cut_summary{s.max_abs, s.min_abs, s.count, s.bad_count, s.max_col, s.min_col};
+      if (lists) {
+        kept += s.count;
+        out->row_starts[first + v + 1] = out->row_starts[first + v] + s.count;
+      }
+    }
+    if (kept > 0) {
+      const size_t old = out->cols.size();
+      out->cols.resize(old + size_t(kept));
+      out->vals.resize(old + size_t(kept));
+      Check(hipMemcpyAsync(out->cols.data() + old, sp.cols, size_t(kept) * sizeof(int32_t),
+                           hipMemcpyDeviceToHost, S(stream_)),
+            "D2H");
+      Download(out->vals.data() + old, sp.vals, size_t(kept) * sizeof(double));
+    }
+    timer.Downloaded();
+    PanelRecord(plan, width, &w.last_cuts.panel);
+    w.last_cuts.kept += kept;
+    w.last_cuts.bytes_down += int64_t(kp) * 32 + (pack ? int64_t(kp) * 8 : 0) + kept * 12;
+  });
+  DeviceOp("column cuts panel done");
 }
 
 bool DeviceLp::ValidOverrides(int num_cols, int k, const int64_t* starts, const int32_t* cols) {

@@ -784,6 +784,59 @@ int LastPenalties(mi_devop* h, mi_devop_penalties* out) {
   });
 }
 
+int ColumnCutsPanel(mi_devop* h, const double* y, int k, const int8_t* status,
+                    const double* unit, const double* f0, const double* row_unit,
+                    double zero_tolerance, double drop_tolerance, int64_t* row_starts,
+                    int32_t* cols, double* vals, int64_t capacity,
+                    mi_devop_cut_summary* summaries) {
+  bool too_large = false;
+  const int rc = Guard(h, [&] {
+    if (!milp::DeviceLp::ValidCutArgs(h->csc.num_cols(), k, status, unit, f0, row_unit,
+                                      zero_tolerance, drop_tolerance)) {
+      throw milp::DeviceError("column_cuts_panel: bad arguments");
+    }
+    milp::DeviceLp::CutRows cuts;
+    h->dev.ColumnCutsPanel(y, k, reinterpret_cast<const uint8_t*>(status), unit, f0, row_unit,
+                           zero_tolerance, drop_tolerance, row_starts != nullptr, &cuts);
+    if (row_starts != nullptr) {
+      const int64_t kept = cuts.row_starts.back();
+      if (kept > capacity) {
+        too_large = true;
+        throw milp::DeviceError("column_cuts_panel: " + std::to_string(kept) +
+                                " entries, capacity " + std::to_string(capacity));
+      }
+      std::memcpy(row_starts, cuts.row_starts.data(), cuts.row_starts.size() * sizeof(int64_t));
+      if (kept > 0) {
+        std::memcpy(cols, cuts.cols.data(), size_t(kept) * sizeof(int32_t));
+        std::memcpy(vals, cuts.vals.data(), size_t(kept) * sizeof(double));
+      }
+    }
+    if (summaries != nullptr && k > 0) {
+      std::memcpy(summaries, cuts.summaries.data(), size_t(k) * sizeof(mi_lp_cut_summary));
+    }
+  });
+  return too_large ? int{MI_DEVOP_CAPACITY} : rc;
+}
+
+int LastCuts(mi_devop* h, mi_devop_cuts* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastCuts p = h->dev.last_cuts();
+    out->sparse = p.panel.sparse;
+    out->dense = p.panel.dense ? 1 : 0;
+    out->panels = p.panel.panels;
+    out->width = p.panel.width;
+    out->tiles = p.tiles;
+    out->structural_tiles = p.structural_tiles;
+    out->lists = p.lists ? 1 : 0;
+    out->reserved = 0;
+    out->kept = p.kept;
+    out->bytes_down = p.bytes_down;
+  });
+}
+
+static_assert(sizeof(mi_devop_cut_summary) == sizeof(mi_lp_cut_summary) &&
+                  offsetof(mi_devop_cut_summary, min_col) == offsetof(mi_lp_cut_summary, min_col),
+              "mi_lp_devop.h restates mi_lp_cut_summary");
 static_assert(sizeof(mi_devop_branch_penalty) == sizeof(mi_lp_branch_penalty) &&
                   offsetof(mi_devop_branch_penalty, up_count) ==
                       offsetof(mi_lp_branch_penalty, up_count),
@@ -838,4 +891,5 @@ extern "C" const mi_devop_api mi_devop_table = {
     BoundPropagatedColumnsFrom,
     LastBoundPropagate,
     ColumnPenaltiesPanel, LastPenalties,
+    ColumnCutsPanel, LastCuts,
 };

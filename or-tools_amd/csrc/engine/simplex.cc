@@ -5732,6 +5732,10 @@ struct mi_lp {
   // that built them: a fifth store.
   milp::DeviceLp::TightenedColumns propagated_columns;
   bool propagated_columns_stored = false;
+  // Likewise the lists of the last mi_lp_row_gomory_cuts / mi_lp_gomory_cuts
+  // call that built them (its summaries are not kept): a sixth store.
+  milp::DeviceLp::CutRows cut_rows;
+  bool cut_rows_stored = false;
   milp::GlopParameters params;
   milp::LinearProgram lp;
   int device = 0;
@@ -6074,6 +6078,7 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t*
   h->infeasible_rows_stored = false;  // mi_lp_get_infeasible_rows: likewise
   h->tightened_columns_stored = false;  // mi_lp_get_tightened_columns: likewise
   h->propagated_columns_stored = false;  // mi_lp_get_propagated_columns: likewise
+  h->cut_rows_stored = false;  // mi_lp_get_cut_rows: likewise
   if ((n > 0 && (clb == nullptr || cub == nullptr || obj == nullptr)) ||
       (m > 0 && (rlb == nullptr || rub == nullptr))) {
     return MI_LP_ERROR_NULL;
@@ -6461,6 +6466,122 @@ int mi_lp_branching_penalties(mi_lp* h, const int32_t* cols, int32_t k, const do
         unit != nullptr ? steps.data() : nullptr, down.data(), up.data(), pivot_tolerance, out);
     return MI_LP_OK;
   });
+}
+
+}  // extern "C"
+
+namespace {
+// What the two cut calls share once their inputs stand: the shard refusal,
+// the argument check, the device call, and then the outputs and the store.
+// Nothing is written or stored unless everything succeeds; `y` is called
+// inside the device scope (it may run the left solves).
+template <typename Vectors>
+int CutsCall(mi_lp* h, int32_t k, const int8_t* status, const double* unit, const double* f0,
+             const double* row_unit, double zero_tolerance, double drop_tolerance,
+             int64_t* row_starts, mi_lp_cut_summary* summaries, Vectors y) {
+  if (!milp::DeviceLp::ValidCutArgs(h->lp.n + h->lp.m, k, status, unit, f0, row_unit,
+                                    zero_tolerance, drop_tolerance)) {
+    return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  return PanelCall(h, [&] {
+    milp::DeviceLp::CutRows result;
+    h->simplex.device().ColumnCutsPanel(y(), k, reinterpret_cast<const uint8_t*>(status), unit,
+                                        f0, row_unit, zero_tolerance, drop_tolerance,
+                                        row_starts != nullptr, &result);
+    if (summaries != nullptr) {
+      std::copy(result.summaries.begin(), result.summaries.end(), summaries);
+    }
+    if (row_starts != nullptr) {
+      std::copy(result.row_starts.begin(), result.row_starts.end(), row_starts);
+      result.summaries.clear();
+      h->cut_rows = std::move(result);
+      h->cut_rows_stored = true;
+    }
+    return MI_LP_OK;
+  });
+}
+
+// The slack part of g would have to be joined across the shards between the
+// two passes; that join is not built.
+bool CutsRefuseShards(mi_lp* h) {
+  if (h->simplex.device().num_shards() <= 1) return false;
+  h->error = "not with column shards";
+  return true;
+}
+}  // namespace
+
+extern "C" {
+
+int mi_lp_row_gomory_cuts(mi_lp* h, const double* y, int32_t k, const int8_t* status,
+                          const double* unit, const double* f0, const double* row_unit,
+                          double zero_tolerance, double drop_tolerance, int64_t* row_starts,
+                          mi_lp_cut_summary* summaries) {
+  if (h == nullptr || y == nullptr || status == nullptr || f0 == nullptr ||
+      row_unit == nullptr || (row_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (CutsRefuseShards(h)) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  return CutsCall(h, k, status, unit, f0, row_unit, zero_tolerance, drop_tolerance, row_starts,
+                  summaries, [&] { return y; });
+}
+
+int mi_lp_gomory_cuts(mi_lp* h, const int32_t* cols, int32_t k, const double* unit,
+                      double zero_tolerance, double drop_tolerance, int64_t* row_starts,
+                      mi_lp_cut_summary* summaries, double* left_inverses) {
+  if (h == nullptr || cols == nullptr || unit == nullptr ||
+      (row_starts == nullptr && summaries == nullptr)) {
+    return MI_LP_ERROR_NULL;
+  }
+  if (!h->solved) return MI_LP_ERROR_STATE;
+  if (CutsRefuseShards(h)) return MI_LP_ERROR_STATE;
+  if (k < 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  const int n = h->lp.n;
+  const int m = h->lp.m;
+  const int total = n + m;
+  const auto& state = h->simplex.GetState();
+  if (state.size() != size_t(total)) return MI_LP_ERROR_STATE;
+  // The basis row of every basic column; -1: not basic.
+  std::vector<int32_t> row_of(size_t(total), -1);
+  for (int r = 0; r < m; ++r) {
+    const int col = h->simplex.GetBasis(r);
+    if (col >= 0 && col < total) row_of[col] = r;
+  }
+  const size_t vectors = static_cast<size_t>(k);
+  const size_t columns = static_cast<size_t>(total);
+  std::vector<int32_t> rows(vectors);
+  std::vector<double> f0(vectors), row_unit(vectors);
+  for (int32_t j = 0; j < k; ++j) {
+    const int32_t col = cols[j];
+    if (col < 0 || col >= n || row_of[col] < 0 || !(unit[col] > 0.0)) {
+      return MI_LP_ERROR_INVALID_PROBLEM;
+    }
+    rows[j] = row_of[col];
+    const double t = h->simplex.GetVariableValue(col) / unit[col];
+    f0[j] = t - std::floor(t);
+    row_unit[j] = unit[col];
+  }
+  std::vector<int8_t> status(columns);
+  for (int col = 0; col < total; ++col) status[col] = static_cast<int8_t>(state[col]);
+  std::vector<double> steps(columns, 0.0);
+  std::copy(unit, unit + n, steps.begin());
+  std::vector<double> local;
+  return CutsCall(h, k, status.data(), steps.data(), f0.data(), row_unit.data(), zero_tolerance,
+                  drop_tolerance, row_starts, summaries, [&] {
+                    return LeftInverses(h, rows.data(), k, left_inverses, &local);
+                  });
+}
+
+int mi_lp_get_cut_rows(const mi_lp* h, int32_t* cols, double* vals) {
+  if (h == nullptr || cols == nullptr || vals == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->cut_rows_stored) return MI_LP_ERROR_STATE;
+  const size_t kept = h->cut_rows.cols.size();
+  if (kept > 0) {
+    std::memcpy(cols, h->cut_rows.cols.data(), kept * sizeof(int32_t));
+    std::memcpy(vals, h->cut_rows.vals.data(), kept * sizeof(double));
+  }
+  return MI_LP_OK;
 }
 
 int mi_lp_column_combinations(mi_lp* h, const double* x, int32_t k, double* out) {

@@ -131,6 +131,58 @@ struct PenaltyArgs {
   BranchPenalty* out;     // kp
 };
 
+// The panel result turned into Gomory mixed-integer cuts in the structural
+// space (panel_kernels.hip, gomory_transform_tile / gomory_combine_tile /
+// gomory_fold; include/mi_lp.h mi_lp_row_gomory_cuts has the rule). All three
+// interleaved arrays share one layout, [col * K + v].
+//   transform  alpha = cols[col * K + v] over all ncols columns -> g: the
+//              structural part to g[col * K + v] (col < n), the slack part to
+//              slack[(col - n) * K + v], which is the row-interleaved vector
+//              y' of the second dot pass; bad-column counts per (vector, tile)
+//              at tile_bad[v * tiles + tile].
+//   combine    s = cols[col * K + v] of the second pass over the n structural
+//              columns -> c = g - s written back to cols; per (vector, tile)
+//              at [v * tiles_n + tile] the kept count, the NaN count, the
+//              largest and the smallest fabs(c) among the kept entries and
+//              the lowest column attaining each. Without a kept entry the
+//              partials are (0.0, kNoCutColumn) and (+inf, kNoCutColumn): a
+//              kept entry has fabs(c) > 0, and a kept +inf sits at a real
+//              column.
+//   fold       workgroup v: one CutSummary.
+struct CutSummary {  // mi_lp_cut_summary of include/mi_lp.h
+  double max_abs;
+  double min_abs;
+  int32_t count;
+  int32_t bad_count;
+  int32_t max_col;
+  int32_t min_col;
+};
+constexpr int kNoCutColumn = 0x7fffffff;
+struct GomoryArgs {
+  double* cols;           // interleaved panel result, ncols x K (c overwrites s for col < n)
+  double* g;              // max(1, n) x K
+  double* slack;          // max(1, m) x K: the dot kernels' y
+  int ncols;              // n + m
+  int n;                  // structural columns
+  int kp;                 // vectors in use (<= K)
+  int tiles;              // ceil(ncols / kPanelTileColumns)
+  int tiles_n;            // ceil(n / kPanelTileColumns)
+  const uint8_t* status;  // ncols: MI_LP_BASIC .. MI_LP_FREE
+  const double* unit;     // ncols: integer steps, or nullptr (all 0)
+  const double* f0;        // kp: the panel's vectors
+  const double* row_unit;  // kp
+  double zero_tolerance;
+  double drop_tolerance;
+  int* tile_bad;           // kp x tiles
+  int* tile_count;         // kp x tiles_n
+  int* tile_nan;           // kp x tiles_n
+  double* tile_max;        // kp x tiles_n
+  double* tile_min;        // kp x tiles_n
+  int32_t* tile_max_col;   // kp x tiles_n
+  int32_t* tile_min_col;   // kp x tiles_n
+  CutSummary* out;         // kp
+};
+
 // Row sums of [A | I] against a panel of K points (panel_kernels.hip,
 // row_sums_panel). The points are column-interleaved, x[col * K + v], zero
 // for the padding points v >= kp; the results are row-interleaved,
@@ -703,6 +755,10 @@ hipError_t panel_deinterleave(int width, const double* in, int ncols, int kp, do
 hipError_t panel_sparse(int width, const milp_kernels::PanelSparseArgs& args, hipStream_t s);
 // penalties_tile, then penalties_fold (kp workgroups), on one stream.
 hipError_t panel_penalties(int width, const milp_kernels::PenaltyArgs& args, hipStream_t s);
+// gomory_transform_tile over the first pass' result; then, after the caller's
+// second dot pass, gomory_combine_tile and gomory_fold (kp workgroups).
+hipError_t panel_gomory_transform(int width, const milp_kernels::GomoryArgs& args, hipStream_t s);
+hipError_t panel_gomory_combine(int width, const milp_kernels::GomoryArgs& args, hipStream_t s);
 // Row sums for a panel of `width` (1, 4 or 16) points in one pass over the
 // rows of [A | I] (panel_kernels.hip row_sums_panel_kernel).
 hipError_t row_sums_panel(int width, const milp_kernels::RowPanelArgs& args, hipStream_t s);

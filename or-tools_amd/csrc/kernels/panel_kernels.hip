@@ -18,7 +18,10 @@
 // the kept (column, value) pairs per vector in increasing column order; it
 // replaces deinterleave_kernel when the caller wants sparse rows. The
 // branching penalties (penalties_tile / penalties_fold, after it) reduce
-// out[col * K + v] to one 32-byte record per vector instead.
+// out[col * K + v] to one 32-byte record per vector instead, and the Gomory
+// cuts (gomory_transform_tile / gomory_combine_tile / gomory_fold, after
+// them) turn it into cut coefficients around a second pass of the dot
+// kernels, which the sparse form then packs.
 //
 // The other direction, row sums [A | I] x for a panel of K points
 // (row_sums_panel_kernel and the kernels that build its interleaved points:
@@ -572,6 +575,268 @@ __global__ __launch_bounds__(kPanelOffsetsStep) void penalties_fold_kernel(Penal
     r.up_col = best_col[1] == kNoPenaltyColumn ? -1 : best_col[1];
     r.down_count = count[0];
     r.up_count = count[1];
+    a.out[v] = r;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Gomory mixed-integer cuts out of the interleaved panel result (include/
+// mi_lp.h mi_lp_row_gomory_cuts has the rule), around a second pass of the
+// dot kernels; penalties_tile's tile and thread layout throughout.
+//   gomory_transform_tile  alpha -> g per (column, vector) over all N columns.
+//                          The structural part goes to a buffer of its own;
+//                          the slack part IS the vector y' of the second dot
+//                          pass (the slack of row r is -(A x)_r), stored
+//                          row-interleaved where the dot kernels read y: slack
+//                          column n + r of the tile lands at element
+//                          (col - n) * K + v, contiguous like the load.
+//   (dot pass)             s = y'^T A, into the panel result again.
+//   gomory_combine_tile    c = g - s over the n structural columns, in place,
+//                          and the per-tile partials of the summary over the
+//                          entries with fabs(c) > drop_tolerance.
+//   gomory_fold            workgroup v folds vector v's partials.
+// The extrema merge to the larger (smaller) value and, among equal values,
+// the lower column; the counts are integer sums: exact and symmetric, the
+// same bits in any reduction order.
+__device__ __forceinline__ void cut_merge_max(double* value, int* col, double other_value,
+                                              int other_col) {
+  if (other_value > *value || (other_value == *value && other_col < *col)) {
+    *value = other_value;
+    *col = other_col;
+  }
+}
+
+// Steps 1-6 of the rule for one (column, vector); every operation rounded on
+// its own. *bad counts a NaN alpha and a FREE column above the tolerance.
+__device__ __forceinline__ double gomory_coefficient(double alpha, int status, double unit,
+                                                     double f0, double row_unit,
+                                                     double zero_tolerance, int* bad) {
+  if (status == 0 || status == 1) return 0.0;  // MI_LP_BASIC, MI_LP_FIXED_VALUE
+  if (alpha != alpha) {
+    ++*bad;
+    return 0.0;
+  }
+  if (!(fabs(alpha) > zero_tolerance)) return 0.0;
+  if (status == 4) {  // MI_LP_FREE
+    ++*bad;
+    return 0.0;
+  }
+  const bool at_lower = status == 2;  // MI_LP_AT_LOWER_BOUND; else MI_LP_AT_UPPER_BOUND
+  const double abar = at_lower ? alpha : -alpha;
+  double gamma;
+  if (unit > 0.0) {
+    const double scaled = abar * unit;
+    const double t = scaled / row_unit;
+    const double f = t - floor(t);
+    gamma = f <= f0 ? f / f0 : (1.0 - f) / (1.0 - f0);
+    gamma = gamma / unit;
+  } else {
+    const double t = abar / row_unit;
+    gamma = t > 0.0 ? t / f0 : (-t) / (1.0 - f0);
+  }
+  return at_lower ? gamma : 0.0 - gamma;
+}
+
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void gomory_transform_tile_kernel(GomoryArgs a) {
+  static_assert(kPanelTileColumns == 256 && kPanelTileColumns % K == 0 && kWave % K == 0,
+                "a thread owns one vector");
+  constexpr int kWaves = kPanelTileColumns / kWave;
+  __shared__ int wave_bad[kWaves][K];
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int col0 = tile * kPanelTileColumns;
+  const int cols = min(kPanelTileColumns, a.ncols - col0);
+  const double* __restrict__ in = a.cols + static_cast<int64_t>(col0) * K;
+  const int v = t % K;
+  const bool live = v < a.kp;
+  const double f0 = live ? a.f0[v] : 0.5;
+  const double row_unit = live ? a.row_unit[v] : 1.0;
+  int bad = 0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const int cl = t / K + j * (kPanelTileColumns / K);
+    if (cl < cols) {
+      const int col = col0 + cl;
+      double g = 0.0;  // the padding slots v >= kp
+      if (live) {
+        const double alpha = in[t + j * kPanelTileColumns];
+        const int status = a.status[col];
+        const double unit = a.unit != nullptr ? a.unit[col] : 0.0;
+        g = gomory_coefficient(alpha, status, unit, f0, row_unit, a.zero_tolerance, &bad);
+      }
+      if (col < a.n) {
+        a.g[static_cast<int64_t>(col) * K + v] = g;
+      } else {
+        a.slack[static_cast<int64_t>(col - a.n) * K + v] = g;
+      }
+    }
+  }
+  // Lanes l, l + K, l + 2K, ... of a wave hold the same vector.
+#pragma unroll
+  for (int off = K; off < kWave; off <<= 1) bad += __shfl_xor(bad, off, kWave);
+  const int lane = t & (kWave - 1);
+  if (lane < K) wave_bad[t / kWave][lane] = bad;  // lane == v
+  __syncthreads();
+  if (t < K && t < a.kp) {
+    int sum = wave_bad[0][t];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += wave_bad[w][t];
+    a.tile_bad[static_cast<int64_t>(t) * a.tiles + tile] = sum;
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(kPanelTileColumns) void gomory_combine_tile_kernel(GomoryArgs a) {
+  static_assert(kPanelTileColumns == 256 && kPanelTileColumns % K == 0 && kWave % K == 0,
+                "a thread owns one vector");
+  constexpr int kWaves = kPanelTileColumns / kWave;
+  __shared__ double wave_max[kWaves][K];
+  __shared__ double wave_min[kWaves][K];
+  __shared__ int wave_max_col[kWaves][K];
+  __shared__ int wave_min_col[kWaves][K];
+  __shared__ int wave_count[kWaves][K];
+  __shared__ int wave_nan[kWaves][K];
+  const int t = threadIdx.x;
+  const int tile = blockIdx.x;
+  const int col0 = tile * kPanelTileColumns;
+  const int cols = min(kPanelTileColumns, a.n - col0);
+  double* __restrict__ s = a.cols + static_cast<int64_t>(col0) * K;
+  const double* __restrict__ g = a.g + static_cast<int64_t>(col0) * K;
+  const int v = t % K;
+  double hi = 0.0;
+  double lo = __builtin_inf();
+  int hi_col = kNoCutColumn;
+  int lo_col = kNoCutColumn;
+  int count = 0;
+  int nan = 0;
+  if (v < a.kp) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const int cl = t / K + j * (kPanelTileColumns / K);
+      if (cl < cols) {
+        const int at = t + j * kPanelTileColumns;
+        const double c = g[at] - s[at];
+        s[at] = c;
+        const double abs_c = fabs(c);
+        if (c != c) ++nan;
+        if (abs_c > a.drop_tolerance) {  // panel_keep's rule without a mask
+          ++count;
+          cut_merge_max(&hi, &hi_col, abs_c, col0 + cl);
+          penalty_merge(&lo, &lo_col, abs_c, col0 + cl);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int off = K; off < kWave; off <<= 1) {
+    count += __shfl_xor(count, off, kWave);
+    nan += __shfl_xor(nan, off, kWave);
+    const double other_hi = __shfl_xor(hi, off, kWave);
+    const int other_hi_col = __shfl_xor(hi_col, off, kWave);
+    cut_merge_max(&hi, &hi_col, other_hi, other_hi_col);
+    const double other_lo = __shfl_xor(lo, off, kWave);
+    const int other_lo_col = __shfl_xor(lo_col, off, kWave);
+    penalty_merge(&lo, &lo_col, other_lo, other_lo_col);
+  }
+  const int lane = t & (kWave - 1);
+  const int wave = t / kWave;
+  if (lane < K) {  // lane == v
+    wave_max[wave][lane] = hi;
+    wave_min[wave][lane] = lo;
+    wave_max_col[wave][lane] = hi_col;
+    wave_min_col[wave][lane] = lo_col;
+    wave_count[wave][lane] = count;
+    wave_nan[wave][lane] = nan;
+  }
+  __syncthreads();
+  if (t < K && t < a.kp) {
+    hi = wave_max[0][t];
+    lo = wave_min[0][t];
+    hi_col = wave_max_col[0][t];
+    lo_col = wave_min_col[0][t];
+    count = wave_count[0][t];
+    nan = wave_nan[0][t];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) {
+      count += wave_count[w][t];
+      nan += wave_nan[w][t];
+      cut_merge_max(&hi, &hi_col, wave_max[w][t], wave_max_col[w][t]);
+      penalty_merge(&lo, &lo_col, wave_min[w][t], wave_min_col[w][t]);
+    }
+    const int64_t at = static_cast<int64_t>(t) * a.tiles_n + tile;
+    a.tile_count[at] = count;
+    a.tile_nan[at] = nan;
+    a.tile_max[at] = hi;
+    a.tile_min[at] = lo;
+    a.tile_max_col[at] = hi_col;
+    a.tile_min_col[at] = lo_col;
+  }
+}
+
+// Workgroup v folds vector v's partials of both kernels into its summary:
+// integer sums (at most ncols < 2^31 each), the exact extrema and the lowest
+// column attaining each (-1 without a kept entry).
+__global__ __launch_bounds__(kPanelOffsetsStep) void gomory_fold_kernel(GomoryArgs a) {
+  constexpr int kWaves = kPanelOffsetsStep / kWave;
+  __shared__ double wave_max[kWaves];
+  __shared__ double wave_min[kWaves];
+  __shared__ int wave_max_col[kWaves];
+  __shared__ int wave_min_col[kWaves];
+  __shared__ int wave_count[kWaves];
+  __shared__ int wave_bad[kWaves];
+  const int t = threadIdx.x;
+  const int v = blockIdx.x;  // < kp: the grid is exactly kp workgroups
+  double hi = 0.0;
+  double lo = __builtin_inf();
+  int hi_col = kNoCutColumn;
+  int lo_col = kNoCutColumn;
+  int count = 0;
+  int bad = 0;
+  const int64_t base_all = static_cast<int64_t>(v) * a.tiles;
+  for (int tile = t; tile < a.tiles; tile += kPanelOffsetsStep) bad += a.tile_bad[base_all + tile];
+  const int64_t base = static_cast<int64_t>(v) * a.tiles_n;
+  for (int tile = t; tile < a.tiles_n; tile += kPanelOffsetsStep) {
+    count += a.tile_count[base + tile];
+    bad += a.tile_nan[base + tile];
+    cut_merge_max(&hi, &hi_col, a.tile_max[base + tile], a.tile_max_col[base + tile]);
+    penalty_merge(&lo, &lo_col, a.tile_min[base + tile], a.tile_min_col[base + tile]);
+  }
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    count += __shfl_xor(count, off, kWave);
+    bad += __shfl_xor(bad, off, kWave);
+    const double other_hi = __shfl_xor(hi, off, kWave);
+    const int other_hi_col = __shfl_xor(hi_col, off, kWave);
+    cut_merge_max(&hi, &hi_col, other_hi, other_hi_col);
+    const double other_lo = __shfl_xor(lo, off, kWave);
+    const int other_lo_col = __shfl_xor(lo_col, off, kWave);
+    penalty_merge(&lo, &lo_col, other_lo, other_lo_col);
+  }
+  if ((t & (kWave - 1)) == 0) {
+    wave_max[t / kWave] = hi;
+    wave_min[t / kWave] = lo;
+    wave_max_col[t / kWave] = hi_col;
+    wave_min_col[t / kWave] = lo_col;
+    wave_count[t / kWave] = count;
+    wave_bad[t / kWave] = bad;
+  }
+  __syncthreads();
+  if (t == 0) {
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) {
+      count += wave_count[w];
+      bad += wave_bad[w];
+      cut_merge_max(&hi, &hi_col, wave_max[w], wave_max_col[w]);
+      penalty_merge(&lo, &lo_col, wave_min[w], wave_min_col[w]);
+    }
+    CutSummary r;
+    r.max_abs = hi;
+    r.min_abs = lo;
+    r.count = count;
+    r.bad_count = bad;
+    r.max_col = hi_col == kNoCutColumn ? -1 : hi_col;
+    r.min_col = lo_col == kNoCutColumn ? -1 : lo_col;
     a.out[v] = r;
   }
 }
@@ -1330,6 +1595,33 @@ hipError_t panel_penalties(int width, const PenaltyArgs& args, hipStream_t s) {
     constexpr int K = decltype(w)::value;
     penalties_tile_kernel<K><<<args.tiles, kPanelTileColumns, 0, s>>>(args);
     penalties_fold_kernel<<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
+  });
+}
+
+static bool gomory_args_ok(const GomoryArgs& args) {
+  return args.n >= 0 && args.n <= args.ncols &&
+         args.tiles == panel_div_up(args.ncols, kPanelTileColumns) &&
+         args.tiles_n == panel_div_up(args.n, kPanelTileColumns);
+}
+
+hipError_t panel_gomory_transform(int width, const GomoryArgs& args, hipStream_t s) {
+  if (args.ncols <= 0 || args.kp <= 0) return hipSuccess;
+  if (!gomory_args_ok(args)) return hipErrorInvalidValue;
+  return for_panel_width(width, [&](auto w) {
+    gomory_transform_tile_kernel<decltype(w)::value>
+        <<<args.tiles, kPanelTileColumns, 0, s>>>(args);
+  });
+}
+
+hipError_t panel_gomory_combine(int width, const GomoryArgs& args, hipStream_t s) {
+  if (args.ncols <= 0 || args.kp <= 0) return hipSuccess;
+  if (!gomory_args_ok(args)) return hipErrorInvalidValue;
+  return for_panel_width(width, [&](auto w) {
+    if (args.tiles_n > 0) {
+      gomory_combine_tile_kernel<decltype(w)::value>
+          <<<args.tiles_n, kPanelTileColumns, 0, s>>>(args);
+    }
+    gomory_fold_kernel<<<args.kp, kPanelOffsetsStep, 0, s>>>(args);
   });
 }
 

@@ -180,6 +180,7 @@ EXPORTED_SYMBOLS = [
     "mi_lp_row_combinations", "mi_lp_get_tableau_rows",
     "mi_lp_row_combinations_sparse", "mi_lp_get_tableau_rows_sparse", "mi_lp_get_sparse_rows",
     "mi_lp_row_penalties", "mi_lp_branching_penalties",
+    "mi_lp_row_gomory_cuts", "mi_lp_gomory_cuts", "mi_lp_get_cut_rows",
     "mi_lp_column_combinations", "mi_lp_column_combinations_from",
     "mi_lp_column_combinations_violations", "mi_lp_column_combinations_from_violations",
     "mi_lp_get_violated_rows",

@@ -430,6 +430,46 @@ def branch_penalties(constraint, trail, x, cols, pivot_tolerance=PENALTY_PIVOT_T
     return out
 
 
+def gomory_cuts(constraint, x, cols, zero_tolerance=PENALTY_PIVOT_TOLERANCE,
+                drop_tolerance=0.0):
+    """Gomory mixed-integer cuts of a solved node, one call for all of `cols`
+    (fractional, hence BASIC, integer columns of the node's LP solution x at
+    CP scale): handle.gomory_cuts (include/mi_lp.h mi_lp_gomory_cuts), the
+    rows, the GMI formula and the slack elimination on the GPU.
+
+    The integer columns' step is one CP unit, their VariableScalingFactor, as
+    in branch_penalties. Cuts with a bad column (a free non-basic column or a
+    NaN in their support) or without a kept coefficient are dropped. Nothing
+    in the rule depends on the objective's sense.
+
+    Returns one dict per remaining cut: "col", the column of `cols` it comes
+    from; "cols" and "coefs", the kept structural columns, ascending, and
+    their coefficients at the LP's scale; "rhs" = 1 + fsum(coefs *
+    x_lp[cols]) with x_lp = x * factor, so that the cut reads
+    sum coefs[i] * x_lp[cols[i]] >= rhs and the node's point violates it by
+    1; "max_abs" and "min_abs", the extreme |coefs| (what a cut loop rejects
+    badly scaled cuts by). At CP scale the same cut is
+    sum (coefs[i] * factor[cols[i]]) * x_cp[cols[i]] >= rhs."""
+    cols = [int(c) for c in cols]
+    factor = constraint.factor
+    unit = np.zeros(constraint.lp.n)
+    unit[constraint.int_cols] = factor[constraint.int_cols]
+    starts, kept_cols, vals, summaries = constraint.h.gomory_cuts(
+        cols, unit, zero_tolerance=zero_tolerance, drop_tolerance=drop_tolerance)
+    x_lp = np.asarray(x, dtype=np.float64) * factor
+    out = []
+    for j, col in enumerate(cols):
+        if int(summaries["bad_count"][j]) > 0 or int(summaries["count"][j]) == 0:
+            continue
+        idx = np.asarray(kept_cols[starts[j]:starts[j + 1]], dtype=np.int64)
+        coefs = np.array(vals[starts[j]:starts[j + 1]], dtype=np.float64)
+        out.append({"col": col, "cols": idx, "coefs": coefs,
+                    "rhs": 1.0 + math.fsum(coefs * x_lp[idx]),
+                    "max_abs": float(summaries["max_abs"][j]),
+                    "min_abs": float(summaries["min_abs"][j])})
+    return out
+
+
 def tightened_overrides(result):
     """LpHandle.tightened_columns(_from)'s result (col_starts, cols, new_lbs,
     new_ubs, summaries) as overrides[j] = (cols, new_lbs, new_ubs), one per

@@ -37,6 +37,10 @@ BRANCH_PENALTY = np.dtype([("down", np.float64), ("up", np.float64), ("down_col"
                            ("up_col", np.int32), ("down_count", np.int32),
                            ("up_count", np.int32)])
 assert BRANCH_PENALTY.itemsize == 32
+# include/mi_lp.h mi_lp_cut_summary: one record per Gomory cut.
+CUT_SUMMARY = np.dtype([("max_abs", np.float64), ("min_abs", np.float64), ("count", np.int32),
+                        ("bad_count", np.int32), ("max_col", np.int32), ("min_col", np.int32)])
+assert CUT_SUMMARY.itemsize == 32
 # mi_lp_propagation (include/mi_lp.h) as a numpy record.
 PROPAGATION = np.dtype([("status", np.int32), ("rounds", np.int32), ("moves", np.int64),
                         ("worst", np.float64), ("worst_col", np.int32), ("kept", np.int32)])
@@ -139,6 +143,11 @@ def lib():
                                       ctypes.c_double, vp]
     L.mi_lp_branching_penalties.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, ctypes.c_double,
                                             vp, vp]
+    L.mi_lp_row_gomory_cuts.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp, ctypes.c_double,
+                                        ctypes.c_double, vp, vp]
+    L.mi_lp_gomory_cuts.argtypes = [vp, vp, ctypes.c_int32, vp, ctypes.c_double, ctypes.c_double,
+                                    vp, vp, vp]
+    L.mi_lp_get_cut_rows.argtypes = [vp, vp, vp]
     L.mi_lp_column_combinations.argtypes = [vp, vp, ctypes.c_int32, vp]
     L.mi_lp_column_combinations_from.argtypes = [vp, vp, ctypes.c_int32, vp, vp, vp, vp]
     L.mi_lp_column_combinations_violations.argtypes = [vp, vp, ctypes.c_int32, vp, vp,
@@ -686,6 +695,86 @@ class LpHandle:
                    None if unit is None else _p(unit), ctypes.c_double(pivot_tolerance),
                    _p(out), None if left is None else _p(left))
         return (out[:k], left[:k]) if with_left_inverses else out[:k]
+
+    def get_cut_rows(self, kept):
+        """The stored lists of the last cut call that built them, `kept`
+        entries (its row_starts[k]): (cols int32, vals float64)."""
+        cols = np.zeros(max(1, kept), np.int32)
+        vals = np.zeros(max(1, kept), np.float64)
+        self._call("get_cut_rows", _p(cols), _p(vals))
+        return cols[:kept], vals[:kept]
+
+    def _cuts(self, name, k, lists, head, tail=()):
+        """The shared tail of the two cut calls: head are the C call's
+        arguments before row_starts, tail those after summaries."""
+        starts = np.zeros(max(k, 1) + 1, np.int64) if lists else None
+        summaries = np.zeros(max(k, 1), CUT_SUMMARY)
+        self._call(name, *head, None if starts is None else _p(starts), _p(summaries), *tail)
+        if not lists:
+            return None, None, None, summaries[:k]
+        cols, vals = self.get_cut_rows(int(starts[k]))
+        return starts[:k + 1], cols, vals, summaries[:k]
+
+    def row_gomory_cuts(self, Y, status, f0, row_unit, unit=None, zero_tolerance=0.0,
+                        drop_tolerance=0.0, lists=True):
+        """One Gomory mixed-integer cut sum c_j x_j >= rhs over the structural
+        columns per row of row_combinations(Y), built on the GPU (include/
+        mi_lp.h mi_lp_row_gomory_cuts has the rule): (row_starts[k+1] int64,
+        cols int32, vals float64, summaries). Cut j's kept columns, ascending,
+        are cols[row_starts[j]:row_starts[j+1]] with the coefficients in vals;
+        summaries is a structured array (CUT_SUMMARY: max_abs, min_abs, count,
+        bad_count, max_col, min_col) of k entries. status and unit cover the
+        n+m columns (unit None: all 0), f0 and row_unit the k vectors. rhs is
+        1 + sum c_j x*_j at the node's LP point and is the caller's to form.
+        With lists=False only the summaries come down and the first three are
+        None."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[None, :]
+        total = self.lp.n + self.lp.m
+        if Y.ndim != 2 or Y.shape[1] != self.lp.m:
+            raise ValueError(f"Y must be (k, {self.lp.m}), got {Y.shape}")
+        k = Y.shape[0]
+        status = np.ascontiguousarray(status, dtype=np.int8)
+        f0 = np.ascontiguousarray(f0, dtype=np.float64).reshape(-1)
+        row_unit = np.ascontiguousarray(row_unit, dtype=np.float64).reshape(-1)
+        if unit is not None:
+            unit = np.ascontiguousarray(unit, dtype=np.float64)
+        if status.shape != (total,) or (unit is not None and unit.shape != (total,)):
+            raise ValueError(f"status and unit must have {total} entries")
+        if len(f0) != k or len(row_unit) != k:
+            raise ValueError(f"f0 and row_unit must have {k} entries")
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            Y = np.zeros((1, self.lp.m), np.float64)
+            f0 = row_unit = np.full(1, 0.5)
+        return self._cuts("row_gomory_cuts", k, lists,
+                          (_p(Y), k, _p(status), None if unit is None else _p(unit), _p(f0),
+                           _p(row_unit), ctypes.c_double(zero_tolerance),
+                           ctypes.c_double(drop_tolerance)))
+
+    def gomory_cuts(self, cols, unit, zero_tolerance=0.0, drop_tolerance=0.0, lists=True,
+                    with_left_inverses=False):
+        """The cuts of the k BASIC structural columns `cols` of the current
+        basis (include/mi_lp.h mi_lp_gomory_cuts): tableau rows, statuses and
+        fractional parts are the solver's; unit: n entries, the integer steps
+        in LP units (0: continuous), positive on every column of cols. Returns
+        what row_gomory_cuts returns; with with_left_inverses also the (k, m)
+        left inverses, last."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        k = len(cols)
+        unit = np.ascontiguousarray(unit, dtype=np.float64)
+        if unit.shape != (self.lp.n,):
+            raise ValueError(f"unit must have {self.lp.n} entries")
+        if k == 0:  # still a call (its state checks), with non-empty buffers behind it
+            cols = np.zeros(1, np.int32)
+        if self.lp.n == 0:
+            unit = np.zeros(1, np.float64)
+        left = np.zeros((max(k, 1), self.lp.m), np.float64) if with_left_inverses else None
+        out = self._cuts("gomory_cuts", k, lists,
+                         (_p(cols), k, _p(unit), ctypes.c_double(zero_tolerance),
+                          ctypes.c_double(drop_tolerance)),
+                         (None if left is None else _p(left),))
+        return out + (left[:k],) if with_left_inverses else out
 
     def _points(self, X, what):
         """X as a contiguous (k, n+m) array: (k, n) gets zero slacks appended,
