@@ -127,6 +127,51 @@ typedef struct mi_devop_cuts {
   int64_t bytes_down; /* device-to-host bytes of the call */
 } mi_devop_cuts;
 
+/* TriKind of engine/device_solver.h: the host loop a device solve replaces. */
+enum {
+  MI_DEVOP_TRI_UPPER_T = 0,    /* TransposeLowerSolve (entries from the column's end) */
+  MI_DEVOP_TRI_LOWER = 1,      /* LowerSolveStartingAt (column scatter) */
+  MI_DEVOP_TRI_UPPER_T_UP = 2, /* TransposeUpperSolve (entries from the column's start) */
+  MI_DEVOP_TRI_LOWER_T = 3,    /* TransposeLowerSolve */
+  MI_DEVOP_TRI_UNIT_ROW = 4,   /* LowerSolveStartingAt */
+  MI_DEVOP_TRI_UPPER = 5       /* UpperSolve (backward column scatter) */
+};
+/* DeviceLp::TriPlan. */
+enum {
+  MI_DEVOP_TRI_PLAN_NONE = 0, /* refused: the host loop runs */
+  MI_DEVOP_TRI_PLAN_TRIVIAL = 1, /* nothing to compute, no launch */
+  MI_DEVOP_TRI_PLAN_SYNC_FREE = 2,
+  MI_DEVOP_TRI_PLAN_PERSISTENT = 3,
+  MI_DEVOP_TRI_PLAN_LEVELS = 4,
+  MI_DEVOP_TRI_PLAN_DENSE_TAIL = 5
+};
+/* DeviceLp::LastTri: the last tri_solve, tri_solve_pair or tri_async_begin. */
+typedef struct mi_devop_tri {
+  int32_t plan; /* MI_DEVOP_TRI_PLAN_* */
+  int32_t kind; /* MI_DEVOP_TRI_* of the schedule */
+  int32_t rows;
+  int32_t first_col;    /* first output of the schedule */
+  int32_t top;          /* last row the solve computes */
+  int32_t work;         /* listed outputs and padding */
+  int32_t pos;          /* positions: work + the rows only read */
+  int32_t levels;
+  int32_t chain_levels; /* levels in single-workgroup segments */
+  int32_t level0_end;   /* positions of a chip-wide level 0 */
+  int32_t wide_runs;    /* sync-free plan: chip-wide launches */
+  int32_t chain_runs;   /* sync-free plan: single-workgroup launches */
+  int32_t chip_launches; /* level plan: levels launched alone over the chip */
+  int32_t cu_runs;      /* level plan: single-CU runs of narrow levels */
+  int32_t fused0;       /* level 0 computed by the gather or init kernel */
+  int32_t vectors;      /* right-hand sides of the launch (2: a pair) */
+  int32_t max_wide_run; /* positions of the largest chip-wide segment */
+  int32_t max_entries;
+  int32_t rows_over[3]; /* outputs of more than 4, 16, 64 entries */
+  int32_t t;            /* dense tail: its first column */
+  int32_t tail_cols;    /* dense tail: T = rows - t */
+  int32_t blocks;       /* dense tail: ceil(T / 64) */
+  int64_t entries;      /* dense tail: entries of its columns */
+} mi_devop_tri;
+
 /* DeviceLp::LastColumnDots: the last launch of the column-dot kernels. */
 typedef struct mi_devop_column_dots {
   int32_t mode;         /* DotMode of simplex_kernels.hip: 1 pricing, 5 pricing with dots */
@@ -432,6 +477,47 @@ typedef struct mi_devop_api {
                            int32_t* cols, double* vals, int64_t capacity,
                            mi_devop_cut_summary* summaries);
   int (*last_cuts)(mi_devop* h, mi_devop_cuts* out);
+  /* Appended after last_cuts. The device triangular solves (engine/
+   * device_solver.h) on a TriangularMatrix owned by the handle; the handle's
+   * own [A | I] plays no part (it may be 1 x 1).
+   *
+   * tri_set_matrix builds the matrix with Reset and AddTriangularColumn:
+   * column c holds the entries [col_starts[c], col_starts[c + 1]) of rows /
+   * vals in the caller's order (none of them on row c) and the diagonal
+   * diag[c]; the first non-identity column and the unit-diagonal flag come out
+   * as the class computes them. Checked here: n >= 1, col_starts[0] == 0,
+   * monotone starts, rows in [0, n) and off the diagonal. NOT checked, the
+   * caller's precondition: the matrix is triangular for the kinds it is
+   * solved with (rows > column for MI_DEVOP_TRI_UPPER_T, _LOWER, _LOWER_T and
+   * _UNIT_ROW; rows < column for _UPPER_T_UP and _UPPER) and no diagonal is
+   * zero. */
+  int (*tri_set_matrix)(mi_devop* h, int n, const int64_t* col_starts, const int32_t* rows,
+                        const double* vals, const double* diag);
+  /* DeviceLp::Solve. kind: MI_DEVOP_TRI_*; key != 0 names the matrix (a new
+   * key rebuilds the schedule); x: n values in and out, untouched when
+   * *on_device == 0. start is the engine's argument of LowerSolveStartingAt:
+   * every x below it must be zero (the engine's own precondition, not
+   * checked). */
+  int (*tri_solve)(mi_devop* h, int kind, uint64_t key, int start, double* x, int* on_device);
+  /* DeviceLp::SolvePair; both vectors untouched when *on_device == 0. */
+  int (*tri_solve_pair)(mi_devop* h, int kind, uint64_t key, double* x0, double* x1,
+                        int* on_device);
+  /* DeviceLp::StartAsyncU / FinishAsyncU / DropAsyncU. finish: x holds the
+   * vector given to begin and receives the result; without a begin before it
+   * it is an error. */
+  int (*tri_async_begin)(mi_devop* h, uint64_t key, const double* x, int* started);
+  int (*tri_async_finish)(mi_devop* h, double* x);
+  int (*tri_async_drop)(mi_devop* h);
+  /* The host loop of the kind on the same matrix (engine/lu.h):
+   * TransposeLowerSolve (_UPPER_T, _LOWER_T), TransposeUpperSolve
+   * (_UPPER_T_UP), LowerSolveStartingAt(start) (_LOWER, _UNIT_ROW), UpperSolve
+   * (_UPPER). */
+  int (*tri_host_solve)(mi_devop* h, int kind, int start, double* x);
+  /* DeviceLp::LastTri: the last tri_solve, tri_solve_pair or tri_async_begin. */
+  int (*last_tri)(mi_devop* h, mi_devop_tri* out);
+  /* The level widths of the schedule last_tri describes: *count of them, the
+   * first min(*count, capacity) written to widths. */
+  int (*last_tri_level_widths)(mi_devop* h, int32_t* widths, int capacity, int* count);
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;

@@ -622,6 +622,36 @@ class DeviceLp : public DeviceSolver {
   void FinishAsyncU(std::vector<double>* x) override;
   void DropAsyncU() override;
   bool SpecFlipEnabled() const { return spec_flip_ && tri_mapped_ && !tri_graph_; }
+  // The last Solve, SolvePair or StartAsyncU of the solver's thread (test
+  // record, host bookkeeping only): the launch plan it went through and the
+  // shape of the schedule (or dense tail) behind it. kTriPlanNone: the call
+  // was refused (the host loop runs).
+  enum TriPlan {
+    kTriPlanNone = 0, kTriPlanTrivial = 1, kTriPlanSyncFree = 2, kTriPlanPersistent = 3,
+    kTriPlanLevels = 4, kTriPlanDenseTail = 5
+  };
+  struct LastTri {
+    int plan = kTriPlanNone;
+    int kind = 0;             // TriKind of the schedule
+    int rows = 0, first_col = 0, top = -1;
+    int work = 0, pos = 0, levels = 0, chain_levels = 0, level0_end = 0;
+    int wide_runs = 0, chain_runs = 0;      // sync-free plan: launches of each kind
+    int chip_launches = 0, cu_runs = 0;     // level plan: chip-wide levels, single-CU runs
+    bool fused0 = false;      // level 0 was computed by the gather / init kernel
+    int vectors = 0;          // right-hand sides of the launch (2: a pair)
+    int max_wide_run = 0, max_entries = 0;
+    int rows_over[3] = {0, 0, 0};
+    int t = 0, tail_cols = 0, blocks = 0;   // dense tail: first column, T, ceil(T / 64)
+    int64_t entries = 0;      // dense tail: entries of its columns
+  };
+  // Assembled on request from the note a solve leaves (four words) and the
+  // schedule or dense tail it names, so ask before the next build.
+  LastTri last_tri() const;
+  // Level widths of the schedule that record describes (none: dense tail).
+  std::vector<int32_t> last_tri_level_widths() const {
+    if (tri_note_.plan == kTriPlanNone || tri_note_.plan == kTriPlanDenseTail) return {};
+    return tri_sched_[tri_note_.which].level_width;
+  }
 
   // Accounting (roofline): launches, algorithmic bytes, HIP-event time.
   void SetTiming(bool on, uint32_t id_mask = ~0u);
@@ -926,8 +956,13 @@ class DeviceLp : public DeviceSolver {
   bool TriSyncFreeFits(const TriSchedule& s) const;
   void TriCopyIn(const TriSchedule& s, const TriContext& c);
   void TriCopyOut(const TriSchedule& s, const TriContext& c);
-  void EnqueueTriKernels(const TriSchedule& s, const milp_kernels::TriSolveArgs& a,
-                         void* stream);
+  // Returns the plan it launched.
+  TriPlan EnqueueTriKernels(const TriSchedule& s, const milp_kernels::TriSolveArgs& a,
+                            void* stream);
+  // The note of a solve on schedule `which` (the solver's thread only).
+  void RecordTri(int which, const TriRun& run, TriPlan plan, int vectors) {
+    tri_note_ = TriNote{plan, which, run.top, vectors};
+  }
   void CaptureTriGraph(int which, TriContext* c);
   void FreeTriBuffers();
 
@@ -1270,6 +1305,11 @@ class DeviceLp : public DeviceSolver {
   std::vector<int64_t> tri_lt_starts_;  // L's rows (gather lists), built per factorization
   std::vector<int32_t> tri_lt_idx_;
   std::vector<double> tri_lt_val_;
+  // What last_tri() is assembled from; written by the solver's thread only.
+  struct TriNote {
+    int plan = kTriPlanNone, which = 0, top = -1, vectors = 0;
+  };
+  TriNote tri_note_;
 };
 
 }  // namespace milp

@@ -2,6 +2,7 @@
 // DeviceLp method, so that a test can run a single device operation on inputs
 // it chooses. A handle owns its CompactSparseMatrix pair and its DeviceLp;
 // there is no RevisedSimplex behind it.
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -12,12 +13,14 @@
 #include "../../../include/mi_lp_devop.h"
 #include "device_lp.h"
 #include "lp_data.h"
+#include "lu.h"
 
 struct mi_devop {
   milp::CompactSparseMatrix csc;  // [A | I]
   milp::CompactSparseMatrix csr;  // its transpose
   milp::DeviceLp dev;
   std::vector<uint64_t> relevant;  // the last kRelevant mask
+  milp::TriangularMatrix tri;      // tri_set_matrix
   std::string error;
 };
 
@@ -834,6 +837,164 @@ int LastCuts(mi_devop* h, mi_devop_cuts* out) {
   });
 }
 
+// --- triangular solves ------------------------------------------------------
+
+int TriCols(const mi_devop* h) {
+  if (h->tri.IsEmpty()) throw milp::DeviceError("no triangular matrix: tri_set_matrix first");
+  return h->tri.num_cols();
+}
+
+milp::TriKind TriKindOf(int kind) {
+  if (kind < 0 || kind >= milp::kNumTriKinds) throw milp::DeviceError("bad triangular kind");
+  return static_cast<milp::TriKind>(kind);
+}
+
+int TriSetMatrix(mi_devop* h, int n, const int64_t* col_starts, const int32_t* rows,
+                 const double* vals, const double* diag) {
+  return Guard(h, [&] {
+    if (n < 1 || col_starts == nullptr || diag == nullptr || col_starts[0] != 0) {
+      throw milp::DeviceError("tri_set_matrix: bad arguments");
+    }
+    for (int c = 0; c < n; ++c) {
+      if (col_starts[c + 1] < col_starts[c]) {
+        throw milp::DeviceError("tri_set_matrix: column starts descend");
+      }
+      for (int64_t i = col_starts[c]; i < col_starts[c + 1]; ++i) {
+        if (rows[i] < 0 || rows[i] >= n || rows[i] == c) {
+          throw milp::DeviceError("tri_set_matrix: row out of range or on the diagonal");
+        }
+      }
+    }
+    // The async solve and the dense tail read the matrix being replaced.
+    h->dev.DropAsyncU();
+    h->tri.Reset(n, n);
+    std::vector<int> r;
+    std::vector<double> v;
+    for (int c = 0; c < n; ++c) {
+      r.assign(rows + col_starts[c], rows + col_starts[c + 1]);
+      v.assign(vals + col_starts[c], vals + col_starts[c + 1]);
+      r.push_back(c);
+      v.push_back(diag[c]);
+      milp::ColumnView view;
+      view.rows = r.data();
+      view.coefs = v.data();
+      view.n = static_cast<int64_t>(r.size());
+      h->tri.AddTriangularColumn(view, c);
+    }
+  });
+}
+
+int TriSolve(mi_devop* h, int kind, uint64_t key, int start, double* x, int* on_device) {
+  return Guard(h, [&] {
+    const int n = TriCols(h);
+    std::vector<double> v(x, x + n);
+    *on_device = h->dev.Solve(TriKindOf(kind), h->tri, key, start, &v) ? 1 : 0;
+    if (*on_device != 0) std::memcpy(x, v.data(), size_t(n) * sizeof(double));
+  });
+}
+
+int TriSolvePair(mi_devop* h, int kind, uint64_t key, double* x0, double* x1, int* on_device) {
+  return Guard(h, [&] {
+    const int n = TriCols(h);
+    std::vector<double> v0(x0, x0 + n), v1(x1, x1 + n);
+    *on_device = h->dev.SolvePair(TriKindOf(kind), h->tri, key, &v0, &v1) ? 1 : 0;
+    if (*on_device != 0) {
+      std::memcpy(x0, v0.data(), size_t(n) * sizeof(double));
+      std::memcpy(x1, v1.data(), size_t(n) * sizeof(double));
+    }
+  });
+}
+
+int TriAsyncBegin(mi_devop* h, uint64_t key, const double* x, int* started) {
+  return Guard(h, [&] {
+    const std::vector<double> v(x, x + TriCols(h));
+    *started = h->dev.StartAsyncU(h->tri, key, v) ? 1 : 0;
+  });
+}
+
+int TriAsyncFinish(mi_devop* h, double* x) {
+  return Guard(h, [&] {
+    const int n = TriCols(h);
+    std::vector<double> v(x, x + n);
+    h->dev.FinishAsyncU(&v);
+    std::memcpy(x, v.data(), size_t(n) * sizeof(double));
+  });
+}
+
+int TriAsyncDrop(mi_devop* h) {
+  return Guard(h, [&] { h->dev.DropAsyncU(); });
+}
+
+int TriHostSolve(mi_devop* h, int kind, int start, double* x) {
+  return Guard(h, [&] {
+    const int n = TriCols(h);
+    std::vector<double> v(x, x + n);
+    switch (TriKindOf(kind)) {
+      case milp::TriKind::kUpperT:
+      case milp::TriKind::kLowerT:
+        h->tri.TransposeLowerSolve(&v);
+        break;
+      case milp::TriKind::kUpperTUp:
+        h->tri.TransposeUpperSolve(&v);
+        break;
+      case milp::TriKind::kLower:
+      case milp::TriKind::kUnitRow:
+        if (start < 0 || start > n) throw milp::DeviceError("tri_host_solve: bad start");
+        h->tri.LowerSolveStartingAt(start, &v);
+        break;
+      case milp::TriKind::kUpper:
+        h->tri.UpperSolve(&v);
+        break;
+    }
+    std::memcpy(x, v.data(), size_t(n) * sizeof(double));
+  });
+}
+
+int LastTri(mi_devop* h, mi_devop_tri* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastTri p = h->dev.last_tri();
+    out->plan = p.plan;
+    out->kind = p.kind;
+    out->rows = p.rows;
+    out->first_col = p.first_col;
+    out->top = p.top;
+    out->work = p.work;
+    out->pos = p.pos;
+    out->levels = p.levels;
+    out->chain_levels = p.chain_levels;
+    out->level0_end = p.level0_end;
+    out->wide_runs = p.wide_runs;
+    out->chain_runs = p.chain_runs;
+    out->chip_launches = p.chip_launches;
+    out->cu_runs = p.cu_runs;
+    out->fused0 = p.fused0 ? 1 : 0;
+    out->vectors = p.vectors;
+    out->max_wide_run = p.max_wide_run;
+    out->max_entries = p.max_entries;
+    for (int i = 0; i < 3; ++i) out->rows_over[i] = p.rows_over[i];
+    out->t = p.t;
+    out->tail_cols = p.tail_cols;
+    out->blocks = p.blocks;
+    out->entries = p.entries;
+  });
+}
+
+int LastTriLevelWidths(mi_devop* h, int32_t* widths, int capacity, int* count) {
+  return Guard(h, [&] {
+    const std::vector<int32_t> w = h->dev.last_tri_level_widths();
+    *count = static_cast<int>(w.size());
+    const size_t k = std::min<size_t>(w.size(), capacity > 0 ? size_t(capacity) : 0);
+    if (k > 0) std::memcpy(widths, w.data(), k * sizeof(int32_t));
+  });
+}
+
+static_assert(int{MI_DEVOP_TRI_UPPER} == static_cast<int>(milp::TriKind::kUpper) &&
+                  int{MI_DEVOP_TRI_UNIT_ROW} == static_cast<int>(milp::TriKind::kUnitRow) &&
+                  int{MI_DEVOP_TRI_UPPER_T_UP} == static_cast<int>(milp::TriKind::kUpperTUp),
+              "mi_lp_devop.h restates TriKind");
+static_assert(int{MI_DEVOP_TRI_PLAN_DENSE_TAIL} == int{milp::DeviceLp::kTriPlanDenseTail} &&
+                  int{MI_DEVOP_TRI_PLAN_LEVELS} == int{milp::DeviceLp::kTriPlanLevels},
+              "mi_lp_devop.h restates DeviceLp's triangular plans");
 static_assert(sizeof(mi_devop_cut_summary) == sizeof(mi_lp_cut_summary) &&
                   offsetof(mi_devop_cut_summary, min_col) == offsetof(mi_lp_cut_summary, min_col),
               "mi_lp_devop.h restates mi_lp_cut_summary");
@@ -892,4 +1053,9 @@ extern "C" const mi_devop_api mi_devop_table = {
     LastBoundPropagate,
     ColumnPenaltiesPanel, LastPenalties,
     ColumnCutsPanel, LastCuts,
+    TriSetMatrix,     TriSolve,
+    TriSolvePair,     TriAsyncBegin,
+    TriAsyncFinish,   TriAsyncDrop,
+    TriHostSolve,     LastTri,
+    LastTriLevelWidths,
 };

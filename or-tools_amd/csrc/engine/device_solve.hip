@@ -511,8 +511,8 @@ bool DeviceLp::TriSyncFreeFits(const TriSchedule& s) const {
          s.levels >= tri_syncfree_min_levels_;
 }
 
-void DeviceLp::EnqueueTriKernels(const TriSchedule& s, const milp_kernels::TriSolveArgs& a,
-                                 void* stream) {
+DeviceLp::TriPlan DeviceLp::EnqueueTriKernels(const TriSchedule& s,
+                                              const milp_kernels::TriSolveArgs& a, void* stream) {
   // The single-launch kernel pays a cross-workgroup hand-off per level; a
   // shallow schedule runs faster as a few level launches.
   if (tri_persist_groups_ > 0 && tri_syncfree_ && a.clock == nullptr &&
@@ -520,19 +520,72 @@ void DeviceLp::EnqueueTriKernels(const TriSchedule& s, const milp_kernels::TriSo
     Check(milp_launch::tri_transpose_lower_persistent(a, tri_persist_groups_, tri_xcd_stride_,
                                                       Stream(stream)),
           "tri persistent");
-    return;
+    return kTriPlanPersistent;
   }
   if (tri_syncfree_ && a.clock == nullptr && TriSyncFreeFits(s)) {
     Check(milp_launch::tri_transpose_lower_syncfree(a, s.runs.data(),
                                                     static_cast<int>(s.runs.size() / 3),
                                                     Stream(stream)),
           "tri syncfree");
-    return;
+    return kTriPlanSyncFree;
   }
   Check(milp_launch::tri_transpose_lower(a, s.segments.data(),
                                          static_cast<int>(s.segments.size() / 2),
                                          Stream(stream)),
         "tri_transpose_lower");
+  return kTriPlanLevels;
+}
+
+// The test record of a solve on schedule `which`: what the plan launched,
+// restated from the schedule (tri_solve.hip's launch loops decide).
+DeviceLp::LastTri DeviceLp::last_tri() const {
+  const int plan = tri_note_.plan, which = tri_note_.which, vectors = tri_note_.vectors;
+  LastTri r;
+  r.plan = plan;
+  r.kind = which;
+  r.top = tri_note_.top;
+  if (plan == kTriPlanNone) return LastTri();
+  if (plan == kTriPlanDenseTail) {
+    const DenseTail& d = dense_tail_;
+    const int T = d.n - d.t;
+    r.rows = d.n;
+    r.first_col = d.fni;
+    r.vectors = 1;
+    r.t = d.t;
+    r.tail_cols = T;
+    r.blocks = (T + 63) / 64;
+    r.entries = d.entries;
+    return r;
+  }
+  const TriSchedule& s = tri_sched_[which];
+  r.rows = s.rows;
+  r.first_col = s.first_col;
+  r.work = s.work;
+  r.pos = s.pos;
+  r.levels = s.levels;
+  r.chain_levels = s.chain_levels;
+  r.level0_end = s.level0_end;
+  r.vectors = vectors;
+  r.max_wide_run = s.max_wide_run;
+  r.max_entries = s.max_entries;
+  for (int i = 0; i < 3; ++i) r.rows_over[i] = s.rows_over[i];
+  if (plan == kTriPlanSyncFree) {
+    const int l0 = tri_fuse0_ ? s.level0_end : 0;
+    r.fused0 = l0 > 0;
+    for (size_t i = 0; i + 2 < s.runs.size(); i += 3) {
+      if (s.runs[i + 1] <= std::max(s.runs[i], l0)) continue;
+      ++(s.runs[i + 2] != 0 ? r.chain_runs : r.wide_runs);
+    }
+  } else if (plan == kTriPlanPersistent) {
+    r.fused0 = tri_fuse0_ && s.level0_end > 0;
+  } else if (plan == kTriPlanLevels) {
+    r.fused0 = tri_fuse0_ && !s.ones && !s.segments.empty() && s.segments[0] == -1;
+    for (size_t i = r.fused0 ? 2 : 0; i + 1 < s.segments.size(); i += 2) {
+      if (s.segments[i + 1] <= s.segments[i]) continue;
+      ++(s.segments[i] < 0 ? r.chip_launches : r.cu_runs);
+    }
+  }
+  return r;
 }
 
 void DeviceLp::CaptureTriGraph(int which, TriContext* c) {
@@ -725,11 +778,13 @@ bool DeviceLp::DenseTailSolve(const TriangularMatrix& u, uint64_t key, std::vect
     throw DeviceError("dense tail solve: dependency wait timed out");
   }
   CopyHost(x + t, d.h_out, sizeof(double) * T);
+  tri_note_ = TriNote{kTriPlanDenseTail, static_cast<int>(TriKind::kUpperTUp), n - 1, 1};
   return true;
 }
 
 bool DeviceLp::Solve(TriKind kind, const TriangularMatrix& t, uint64_t key, int /*start*/,
                      std::vector<double>* x) {
+  if (g_lu_slot == 0) tri_note_.plan = kTriPlanNone;
   if (kind == TriKind::kUpperTUp && DenseTailSolve(t, key, x)) return true;
   // LowerSolveStartingAt(start): the loops below `start` only meet zeros in
   // every caller (a unit row, or L's input below its first non-zero), which
@@ -958,7 +1013,10 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
   TriContext& c = tri_ctx_[slot];
   TriSchedule& s = tri_sched_[which];
   const TriRun run = TriBegin(kind, s, x->data());
-  if (run.trivial) return true;
+  if (run.trivial) {
+    if (slot == 0) RecordTri(which, run, kTriPlanTrivial, 1);
+    return true;
+  }
   FtranTimer ft(kFtDevCopyIn);
   TriStageIn(c, x->data(), run);
   ft.Lap(kFtDevRun);
@@ -975,7 +1033,8 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
     if (s.levels + 1 < 65536) a.clock = d_tri_clock_;
     TriCopyIn(s, c);
     BeginKernel(id);
-    EnqueueTriKernels(s, a, c.stream);
+    const TriPlan plan = EnqueueTriKernels(s, a, c.stream);
+    if (slot == 0) RecordTri(which, run, plan, 1);
     EndKernel(id, run.bytes);
     TriCopyOut(s, c);
     // The armed MPF right-pool append reads the FTRAN vector before it is
@@ -1019,7 +1078,8 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
                            Stream(c.stream)),
             "graph launch");
     } else {
-      EnqueueTriKernels(s, TriArgs(s, c), c.stream);
+      const TriPlan plan = EnqueueTriKernels(s, TriArgs(s, c), c.stream);
+      if (slot == 0) RecordTri(which, run, plan, 1);
     }
     if (slot == 0) {
       EndKernel(id, run.bytes);
@@ -1046,6 +1106,7 @@ bool DeviceLp::TriSolve(int which, const TriangularMatrix& t, uint64_t key,
 // outputs are computed exactly as a single solve computes them.
 bool DeviceLp::SolvePair(TriKind kind, const TriangularMatrix& t, uint64_t key,
                          std::vector<double>* x0, std::vector<double>* x1) {
+  if (g_lu_slot == 0) tri_note_.plan = kTriPlanNone;
   if (kind != TriKind::kUpperT || !tri_pair_ || g_lu_slot != 0) return false;
   if (!tri_syncfree_ || !tri_mapped_ || tri_graph_ || tri_persist_groups_ > 0) return false;
   if (tri_debug_left_ > 0) return false;
@@ -1082,6 +1143,7 @@ bool DeviceLp::SolvePair(TriKind kind, const TriangularMatrix& t, uint64_t key,
                                                   static_cast<int>(s.runs.size() / 3),
                                                   Stream(c0.stream), 2),
         "tri pair");
+  RecordTri(kTriU, runs[0], kTriPlanSyncFree, 2);
   EndKernel(MI_K_TRI_SOLVE, runs[0].bytes + runs[1].bytes);
   g_overlap.Run();  // host work behind the device's
   DeviceOp("tri pair sync");
@@ -1094,6 +1156,7 @@ bool DeviceLp::SolvePair(TriKind kind, const TriangularMatrix& t, uint64_t key,
 // StartAsyncU): TriSolve's staging and launch plan on slot 3's stream, with
 // no wait; FinishAsyncU waits and copies the result back as TriSolve does.
 bool DeviceLp::StartAsyncU(const TriangularMatrix& t, uint64_t key, const std::vector<double>& x) {
+  if (g_lu_slot == 0) tri_note_.plan = kTriPlanNone;
   if (g_lu_slot != 0 || !spec_flip_ || !tri_mapped_ || tri_graph_ || tri_debug_left_ > 0) {
     return false;
   }
@@ -1103,14 +1166,17 @@ bool DeviceLp::StartAsyncU(const TriangularMatrix& t, uint64_t key, const std::v
   TriSchedule& s = tri_sched_[kTriU];
   async_u_.run = TriBegin(TriKind::kUpperT, s, x.data());
   async_u_.active = true;
-  if (async_u_.run.trivial) return true;
+  if (async_u_.run.trivial) {
+    RecordTri(kTriU, async_u_.run, kTriPlanTrivial, 1);
+    return true;
+  }
   DeviceOp("tri U async enter");
   TriStageIn(c, x.data(), async_u_.run);
   async_u_.timed = Timed(MI_K_TRI_SOLVE);
   if (async_u_.timed) {
     Check(hipEventRecord(reinterpret_cast<hipEvent_t>(c.ev[0]), Stream(c.stream)), "ev");
   }
-  EnqueueTriKernels(s, TriArgs(s, c), c.stream);
+  RecordTri(kTriU, async_u_.run, EnqueueTriKernels(s, TriArgs(s, c), c.stream), 1);
   if (async_u_.timed) {
     Check(hipEventRecord(reinterpret_cast<hipEvent_t>(c.ev[1]), Stream(c.stream)), "ev");
   }
