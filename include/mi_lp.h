@@ -217,6 +217,59 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* col_starts,
                const double* obj, double obj_offset, double obj_scale,
                int32_t maximize);
 
+/* Appends k rows to the loaded LP (the cuts of a cut loop). The rows are lists,
+ * the shape mi_lp_get_cut_rows returns: row j holds (cols[p], vals[p]) for p in
+ * [row_starts[j], row_starts[j + 1]), row_starts has k + 1 entries, and per
+ * row the structural columns are strictly ascending in [0, n), the
+ * coefficients finite and non-zero; row_lb / row_ub may be +/-INFINITY (a
+ * Gomory cut is row_lb = rhs, row_ub = +INFINITY). Row j becomes row m + j and
+ * its slack column n + m + j; old columns and old slacks keep their indices.
+ *
+ * The contract: in any sequence of calls on a handle, replacing
+ * mi_lp_add_rows(R) by mi_lp_load of the extended LP (the same columns, each
+ * with R's entries appended, and the handle's current column bounds,
+ * objective, offset, scale and sense) changes no bit of anything the handle
+ * later returns: solve results, iterations, basis, state and rays, every panel
+ * call (refused until the next solve, as after a load),
+ * mi_lp_batch_solve_bounds (the matrix fingerprint is that of the load) and
+ * the stores of the mi_lp_get_* lists (forgotten, as on a load). That holds
+ * before a first solve, after mi_lp_load_basis_state, for two appends in a
+ * row, and for a mi_lp_load between an append and the solve. Only the time
+ * and the bytes moved differ: where the handle's matrix is resident on the
+ * device (it has been solved since its last load), only the new rows cross
+ * PCIe, they are merged into the resident CSC and CSR on the device, and the
+ * next solve takes the warm new-rows path of
+ * RevisedSimplex::Initialize (revised_simplex.cc:1334-1565) without the
+ * entry-by-entry compare, the host rebuild or the upload. The host still
+ * shifts its own columns and re-hashes A (one pass each). One exception to
+ * the contract: after mi_lp_notify_matrix_unchanged the load twin would
+ * solve on the stale matrix; the append is honoured instead.
+ *
+ * k = 0 succeeds and is the load of the same LP.
+ *
+ *   MI_LP_ERROR_NULL             h or row_starts NULL; cols or vals NULL with
+ *                                row_starts[k] > 0; row_lb or row_ub NULL with
+ *                                k > 0
+ *   MI_LP_ERROR_STATE            before mi_lp_load, or while a begun solve runs
+ *   MI_LP_ERROR_INVALID_PROBLEM  k < 0; row_starts[0] != 0 or decreasing
+ *                                row_starts; a column out of range or not
+ *                                strictly ascending; a zero, NaN or infinite
+ *                                coefficient; a NaN bound; n + m + k past
+ *                                int32 or nnz + e + m + k past int64
+ * On every error nothing changes, neither on the host nor on the device. */
+typedef struct mi_lp_append_info {
+  int32_t path;      /* 0: no device matrix yet (host only); 1: merged on the device;
+                        2: full upload from the extended host matrices (column
+                        shards, or 32768 rows and more) */
+  int32_t rows;      /* k */
+  int64_t entries;   /* e = row_starts[k] */
+  int64_t bytes_up;  /* bytes sent host -> device by this call for the matrix:
+                        on path 1 at most 12 (e + k) + 8 k */
+} mi_lp_append_info;
+int mi_lp_add_rows(mi_lp* h, int32_t k, const int64_t* row_starts, const int32_t* cols,
+                   const double* vals, const double* row_lb, const double* row_ub,
+                   mi_lp_append_info* info /* may be NULL */);
+
 /* statuses: n+m glop::VariableStatus values (structural then slacks). */
 int mi_lp_load_basis_state(mi_lp* h, const int8_t* statuses, int32_t len);
 int mi_lp_clear_basis_state(mi_lp* h);

@@ -6,7 +6,8 @@
  * the MILP_* environment switches (DeviceLp::Init), so a test sets the
  * environment first and creates the handle afterwards.
  *
- * The library exports one read-only table, mi_devop_table, instead of one
+ * The library exports read-only tables, mi_devop_table and (for the matrix
+ * entries at the end of this file) mi_devop_matrix_table, instead of one
  * function per call: the exported functions of libmi_lp.so stay exactly those
  * of mi_lp.h. Every call returns 0, or non-zero with a message in
  * last_error(h) (a failed create: last_error(NULL), per thread). No C++
@@ -171,6 +172,18 @@ typedef struct mi_devop_tri {
   int32_t blocks;       /* dense tail: ceil(T / 64) */
   int64_t entries;      /* dense tail: entries of its columns */
 } mi_devop_tri;
+
+/* DeviceLp::LastAppend: the last append_rows. */
+enum { MI_DEVOP_MOVE_COLUMN_PER_THREAD = 1, MI_DEVOP_MOVE_COLUMN_PER_WORKGROUP = 2 };
+typedef struct mi_devop_append {
+  int32_t path;        /* 1 merged on the device, 2 full upload */
+  int32_t rows;        /* k */
+  int64_t entries;     /* structural entries of the new rows */
+  int64_t bytes_up;    /* host -> device for the matrix */
+  int32_t move_shapes; /* MI_DEVOP_MOVE_* bits of the move kernels that ran */
+  int32_t reserved;
+  double device_ms;    /* copies and merge kernels, by events */
+} mi_devop_append;
 
 /* DeviceLp::LastColumnDots: the last launch of the column-dot kernels. */
 typedef struct mi_devop_column_dots {
@@ -521,6 +534,29 @@ typedef struct mi_devop_api {
 } mi_devop_api;
 
 extern const mi_devop_api mi_devop_table;
+
+/* The matrix entries, in a table of their own behind mi_devop_table (whose
+ * length tests/test_tri_ref_cpu.py pins): mi_devop_matrix_table. */
+typedef struct mi_devop_matrix_api {
+  /* k rows as lists (include/mi_lp.h mi_lp_add_rows; checked here as that
+   * call checks them) extend the handle's csc / csr on the host
+   * (CompactSparseMatrix::AppendRows, AppendTransposedRows) and the device
+   * with DeviceLp::AppendRows. The relevant mask the handle remembers is all
+   * ones afterwards, as after create. */
+  int (*append_rows)(mi_devop* h, int k, const int64_t* row_starts, const int32_t* cols,
+                     const double* vals);
+  /* The matrix as the device holds it: CSC starts (N + 1) / rows / vals (nnz
+   * each), CSR starts (m + 1) / cols / vals, *nd dense columns in dense_cols
+   * (room for n), and the dense block in dense_block (body then tail, nd * m
+   * values; more than `capacity` returns MI_DEVOP_CAPACITY with only *nd
+   * written). */
+  int (*fetch_matrix)(mi_devop* h, int64_t* starts, int32_t* rows, double* vals,
+                      int64_t* t_starts, int32_t* t_cols, double* t_vals, int32_t* nd,
+                      int32_t* dense_cols, double* dense_block, int64_t capacity);
+  int (*last_append)(mi_devop* h, mi_devop_append* out);
+} mi_devop_matrix_api;
+
+extern const mi_devop_matrix_api mi_devop_matrix_table;
 
 #ifdef __cplusplus
 }

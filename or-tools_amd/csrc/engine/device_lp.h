@@ -66,6 +66,33 @@ class DeviceLp : public DeviceSolver {
 
   // Uploads [A | I] in CSC and CSR (transpose) and sizes every scratch buffer.
   void UploadMatrix(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr);
+  // (csc, csr) are the resident pair extended by k rows on the host
+  // (CompactSparseMatrix::AppendRows / AppendTransposedRows). Only the k new
+  // CSR rows are uploaded; the CSC is merged on the device
+  // (matrix_kernels.hip) and every buffer sized by (m, N) is re-made, so that
+  // the members equal what UploadMatrix(csc, csr) leaves. Old and new matrix
+  // arrays coexist for the length of the call. With column shards, or
+  // kAppendMaxRows rows and more, it is UploadMatrix(csc, csr).
+  void AppendRows(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr, int k);
+  static constexpr int kAppendMaxRows = 1 << 15;  // the tile scans count in int
+  struct LastAppend {
+    int path = 0;          // 1 merged on the device, 2 full upload
+    int rows = 0;
+    int64_t entries = 0;   // structural entries of the new rows
+    int64_t bytes_up = 0;  // host -> device for the matrix
+    int move_shapes = 0;   // bit 0: column per thread ran, bit 1: column per workgroup
+    double device_ms = 0.0;  // copies and merge kernels, by events
+  };
+  LastAppend last_append() const { return last_append_; }
+  // The resident matrix as the device holds it (test support; not on a
+  // solve's path): CSC, CSR, the dense column list and the dense block (body,
+  // then tail, as BuildDenseBlock packs them).
+  struct MatrixCopy {
+    std::vector<int64_t> starts, t_starts;
+    std::vector<int32_t> rows, t_cols, dense_cols;
+    std::vector<double> vals, t_vals, dense_block;
+  };
+  void FetchMatrix(MatrixCopy* out);
 
   // Bit masks over the N columns; uploaded only when the words change.
   enum Mask { kRelevant = 0, kBasic = 1, kNotBasic = 2, kNumMasks = 3 };
@@ -922,6 +949,11 @@ class DeviceLp : public DeviceSolver {
   void CopyHost(void* dst, const void* src, size_t bytes);
   void AccountList(const std::vector<int>& positions);
   void BuildDenseBlock();
+  // The two halves of UploadMatrix around the matrix arrays (AppendRows
+  // shares them).
+  void SetMatrixShape(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr);
+  void AllocateForShape();
+  LastAppend last_append_;
   // Launches the CSC kernel over the sparse columns (all columns when there is
   // no dense block) and the dense-block kernel; mode as in column_dot.
   void LaunchColumnDots(int mode, const double* d_y, const double* d_c, double* d_out,

@@ -748,6 +748,27 @@ void DeviceLp::UploadMatrix(const CompactSparseMatrix& csc, const CompactSparseM
   SetStreamPriority(stream_priority_);
   for (void* p : allocations_) (void)hipFree(p);
   allocations_.clear();
+  SetMatrixShape(csc, csr);
+  d_starts_ = Alloc<int64_t>(n_total_ + 1);
+  d_rows_ = Alloc<int32_t>(nnz_);
+  d_vals_ = Alloc<double>(nnz_);
+  d_t_starts_ = Alloc<int64_t>(m_ + 1);
+  d_t_cols_ = Alloc<int32_t>(nnz_);
+  d_t_vals_ = Alloc<double>(nnz_);
+  Upload(d_starts_, csc.starts_.data(), (n_total_ + 1) * sizeof(int64_t));
+  Upload(d_rows_, csc.rows_.data(), nnz_ * sizeof(int32_t));
+  Upload(d_vals_, csc.coefficients_.data(), nnz_ * sizeof(double));
+  Upload(d_t_starts_, csr.starts_.data(), (m_ + 1) * sizeof(int64_t));
+  Upload(d_t_cols_, csr.rows_.data(), nnz_ * sizeof(int32_t));
+  Upload(d_t_vals_, csr.coefficients_.data(), nnz_ * sizeof(double));
+  AllocateForShape();
+  BuildDenseBlock();
+  Synchronize();
+  if (!shards_.empty()) ShardedUpload(csc);
+}
+
+// The host-side figures of the matrix that the launch decisions read.
+void DeviceLp::SetMatrixShape(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr) {
   m_ = csc.num_rows();
   n_total_ = csc.num_cols();
   nnz_ = csc.num_entries();
@@ -764,18 +785,11 @@ void DeviceLp::UploadMatrix(const CompactSparseMatrix& csc, const CompactSparseM
   for (int r = 0; r < m_; ++r) {
     h_row_full_[r] = (csr.starts_[r + 1] - csr.starts_[r] == int64_t(num_structural_) + 1) ? 1 : 0;
   }
-  d_starts_ = Alloc<int64_t>(n_total_ + 1);
-  d_rows_ = Alloc<int32_t>(nnz_);
-  d_vals_ = Alloc<double>(nnz_);
-  d_t_starts_ = Alloc<int64_t>(m_ + 1);
-  d_t_cols_ = Alloc<int32_t>(nnz_);
-  d_t_vals_ = Alloc<double>(nnz_);
-  Upload(d_starts_, csc.starts_.data(), (n_total_ + 1) * sizeof(int64_t));
-  Upload(d_rows_, csc.rows_.data(), nnz_ * sizeof(int32_t));
-  Upload(d_vals_, csc.coefficients_.data(), nnz_ * sizeof(double));
-  Upload(d_t_starts_, csr.starts_.data(), (m_ + 1) * sizeof(int64_t));
-  Upload(d_t_cols_, csr.rows_.data(), nnz_ * sizeof(int32_t));
-  Upload(d_t_vals_, csr.coefficients_.data(), nnz_ * sizeof(double));
+}
+
+// Every buffer sized by (m, N) but the matrix arrays, which the caller
+// (UploadMatrix, AppendRows) has allocated on an otherwise empty list.
+void DeviceLp::AllocateForShape() {
   mask_words_ = (n_total_ + 63) / 64;
   for (int k = 0; k < kNumMasks; ++k) {
     d_masks_[k] = Alloc<uint64_t>(mask_words_);
@@ -910,9 +924,146 @@ void DeviceLp::UploadMatrix(const CompactSparseMatrix& csc, const CompactSparseM
   dual_ready_ = false;
   last_list_len_ = 0;
   ++list_epoch_;
+}
+
+void DeviceLp::AppendRows(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr, int k) {
+  last_append_ = LastAppend{};
+  last_append_.rows = k;
+  if (!shards_.empty() || k >= kAppendMaxRows) {
+    // Column shards hold slices of their own, and the tile scans count in
+    // int: the existing upload from the extended pair.
+    UploadMatrix(csc, csr);
+    last_append_.path = 2;
+    const int rows = csr.num_cols();
+    last_append_.entries = csr.starts_[rows] - csr.starts_[rows - k] - k;
+    last_append_.bytes_up = (csc.num_cols() + 1 + csr.num_cols() + 1) * int64_t(sizeof(int64_t)) +
+                            2 * csc.num_entries() * int64_t(sizeof(int32_t) + sizeof(double));
+    return;
+  }
+  Check(hipSetDevice(device_), "hipSetDevice");
+  SetStreamPriority(stream_priority_);
+  if (batch_pending_) WaitSmallBatch();
+  Check(hipStreamSynchronize(S(stream_)), "sync");
+  const int old_m = m_;
+  const int n = n_total_ - m_;
+  const int64_t old_nnz = nnz_;
+  if (csc.num_rows() != old_m + k || csc.num_cols() != n_total_ + k ||
+      csr.num_cols() != old_m + k || csc.num_entries() != csr.num_entries() ||
+      csc.num_entries() < old_nnz + k) {
+    throw DeviceError("AppendRows: the extended matrices do not extend the resident one");
+  }
+  const int64_t e = csc.num_entries() - old_nnz - k;
+  last_append_.entries = e;
+  // The old matrix stays until the merge is done; everything else sized by
+  // the old shape goes first.
+  int64_t* old_starts = d_starts_;
+  int32_t* old_rows = d_rows_;
+  double* old_vals = d_vals_;
+  int64_t* old_t_starts = d_t_starts_;
+  int32_t* old_t_cols = d_t_cols_;
+  double* old_t_vals = d_t_vals_;
+  void* const keep[6] = {old_starts, old_rows, old_vals, old_t_starts, old_t_cols, old_t_vals};
+  for (void* p : allocations_) {
+    if (std::find(keep, keep + 6, p) == keep + 6) (void)hipFree(p);
+  }
+  allocations_.assign(keep, keep + 6);
+  bool long_columns = false;  // of the old structural columns, which are what moves
+  for (int c = 0; c < n && !long_columns; ++c) {
+    long_columns = h_starts_[c + 1] - h_starts_[c] > milp_kernels::kAppendShortColumn;
+  }
+  SetMatrixShape(csc, csr);
+  d_starts_ = Alloc<int64_t>(n_total_ + 1);
+  d_rows_ = Alloc<int32_t>(nnz_);
+  d_vals_ = Alloc<double>(nnz_);
+  d_t_starts_ = Alloc<int64_t>(m_ + 1);
+  d_t_cols_ = Alloc<int32_t>(nnz_);
+  d_t_vals_ = Alloc<double>(nnz_);
+  milp_kernels::MatrixAppendArgs a{};
+  a.n = n;
+  a.m = old_m;
+  a.k = k;
+  a.nnz = old_nnz;
+  a.e = e;
+  a.tiles = (n + milp_kernels::kAppendTileColumns - 1) / milp_kernels::kAppendTileColumns;
+  a.add = Alloc<int>(n);
+  a.rank = Alloc<int>(e + k);
+  a.tile_counts = Alloc<int>(a.tiles);
+  a.tile_offsets = Alloc<int64_t>(a.tiles);
+  hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(ev_start_);
+  hipEvent_t ev1 = reinterpret_cast<hipEvent_t>(ev_stop_);
+  Check(hipEventRecord(ev0, S(stream_)), "event");
+  // CSR: the old arrays device to device, the k new rows behind them from the
+  // host. They are all that is uploaded, and the CSC merge reads them there.
+  const auto d2d = [this](void* dst, const void* src, size_t bytes) {
+    if (bytes == 0) return;
+    Check(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, S(stream_)), "D2D");
+  };
+  d2d(d_t_starts_, old_t_starts, (old_m + 1) * sizeof(int64_t));
+  d2d(d_t_cols_, old_t_cols, old_nnz * sizeof(int32_t));
+  d2d(d_t_vals_, old_t_vals, old_nnz * sizeof(double));
+  Upload(d_t_starts_ + old_m + 1, csr.starts_.data() + old_m + 1, k * sizeof(int64_t));
+  Upload(d_t_cols_ + old_nnz, csr.rows_.data() + old_nnz, (e + k) * sizeof(int32_t));
+  Upload(d_t_vals_ + old_nnz, csr.coefficients_.data() + old_nnz, (e + k) * sizeof(double));
+  last_append_.bytes_up =
+      k * int64_t(sizeof(int64_t)) + (e + k) * int64_t(sizeof(int32_t) + sizeof(double));
+  Check(hipMemsetAsync(a.add, 0, std::max(1, n) * sizeof(int), S(stream_)), "memset");
+  a.tail_starts = d_t_starts_ + old_m;
+  a.t_cols = d_t_cols_;
+  a.t_vals = d_t_vals_;
+  a.old_starts = old_starts;
+  a.old_rows = old_rows;
+  a.old_vals = old_vals;
+  a.new_starts = d_starts_;
+  a.new_rows = d_rows_;
+  a.new_vals = d_vals_;
+  Check(milp_launch::matrix_append_rows(a, long_columns, S(stream_)), "append rows");
+  Check(hipEventRecord(ev1, S(stream_)), "event");
+  Check(hipStreamSynchronize(S(stream_)), "sync");  // also: the uploads read pageable memory
+  float ms = 0.0f;
+  Check(hipEventElapsedTime(&ms, ev0, ev1), "elapsed");
+  last_append_.device_ms = ms;
+  last_append_.path = 1;
+  last_append_.move_shapes = n > 0 ? (long_columns ? 3 : 1) : 0;
+  // The old matrix and the merge's scratch go; the six new arrays stay, in
+  // UploadMatrix's order.
+  void* const now[6] = {d_starts_, d_rows_, d_vals_, d_t_starts_, d_t_cols_, d_t_vals_};
+  for (void* p : allocations_) {
+    if (std::find(now, now + 6, p) == now + 6) (void)hipFree(p);
+  }
+  allocations_.assign(now, now + 6);
+  AllocateForShape();
   BuildDenseBlock();
   Synchronize();
-  if (!shards_.empty()) ShardedUpload(csc);
+}
+
+void DeviceLp::FetchMatrix(MatrixCopy* out) {
+  Check(hipSetDevice(device_), "hipSetDevice");
+  Synchronize();
+  out->starts.resize(n_total_ + 1);
+  out->rows.resize(nnz_);
+  out->vals.resize(nnz_);
+  out->t_starts.resize(m_ + 1);
+  out->t_cols.resize(nnz_);
+  out->t_vals.resize(nnz_);
+  const int steps = m_ >> 2;
+  const size_t body = static_cast<size_t>(steps) * nd_ * 4;
+  const size_t tail = static_cast<size_t>(m_ - 4 * steps) * nd_;
+  out->dense_cols.resize(nd_);
+  out->dense_block.resize(body + tail);
+  const auto get = [this](void* dst, const void* src, size_t bytes) {
+    if (bytes > 0) Check(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), "D2H");
+  };
+  get(out->starts.data(), d_starts_, out->starts.size() * sizeof(int64_t));
+  get(out->rows.data(), d_rows_, nnz_ * sizeof(int32_t));
+  get(out->vals.data(), d_vals_, nnz_ * sizeof(double));
+  get(out->t_starts.data(), d_t_starts_, out->t_starts.size() * sizeof(int64_t));
+  get(out->t_cols.data(), d_t_cols_, nnz_ * sizeof(int32_t));
+  get(out->t_vals.data(), d_t_vals_, nnz_ * sizeof(double));
+  if (nd_ > 0) {
+    get(out->dense_cols.data(), d_dense_cols_, nd_ * sizeof(int32_t));
+    get(out->dense_block.data(), d_dense_body_, body * sizeof(double));
+    get(out->dense_block.data() + body, d_dense_tail_, tail * sizeof(double));
+  }
 }
 
 // Full structural columns go to the value-only dense block (8 B per entry

@@ -988,6 +988,64 @@ int LastTriLevelWidths(mi_devop* h, int32_t* widths, int capacity, int* count) {
   });
 }
 
+int AppendRows(mi_devop* h, int k, const int64_t* row_starts, const int32_t* cols,
+               const double* vals) {
+  return Guard(h, [&] {
+    const int n = h->csc.num_cols() - h->csc.num_rows();
+    if (k < 0 || row_starts == nullptr || !milp::ValidRowLists(n, k, row_starts, cols, vals)) {
+      throw milp::DeviceError("append_rows: bad row lists");
+    }
+    h->csc.AppendRows(n, k, row_starts, cols, vals);
+    h->csr.AppendTransposedRows(k, row_starts, cols, vals);
+    h->dev.AppendRows(h->csc, h->csr, k);
+    h->relevant.assign((h->csc.num_cols() + 63) / 64, ~0ull);
+  });
+}
+
+int FetchMatrix(mi_devop* h, int64_t* starts, int32_t* rows, double* vals, int64_t* t_starts,
+                int32_t* t_cols, double* t_vals, int32_t* nd, int32_t* dense_cols,
+                double* dense_block, int64_t capacity) {
+  int rc = 0;
+  const int guarded = Guard(h, [&] {
+    milp::DeviceLp::MatrixCopy c;
+    h->dev.FetchMatrix(&c);
+    if (static_cast<int64_t>(c.starts.size()) != h->csc.num_cols() + 1 ||
+        static_cast<int64_t>(c.rows.size()) != h->csc.num_entries()) {
+      throw milp::DeviceError("fetch_matrix: the device's shape is not the handle's");
+    }
+    *nd = static_cast<int32_t>(c.dense_cols.size());
+    if (static_cast<int64_t>(c.dense_block.size()) > capacity) {
+      rc = MI_DEVOP_CAPACITY;
+      return;
+    }
+    const auto put = [](void* dst, const void* src, size_t bytes) {
+      if (bytes > 0) std::memcpy(dst, src, bytes);
+    };
+    put(starts, c.starts.data(), c.starts.size() * sizeof(int64_t));
+    put(rows, c.rows.data(), c.rows.size() * sizeof(int32_t));
+    put(vals, c.vals.data(), c.vals.size() * sizeof(double));
+    put(t_starts, c.t_starts.data(), c.t_starts.size() * sizeof(int64_t));
+    put(t_cols, c.t_cols.data(), c.t_cols.size() * sizeof(int32_t));
+    put(t_vals, c.t_vals.data(), c.t_vals.size() * sizeof(double));
+    put(dense_cols, c.dense_cols.data(), c.dense_cols.size() * sizeof(int32_t));
+    put(dense_block, c.dense_block.data(), c.dense_block.size() * sizeof(double));
+  });
+  return guarded != 0 ? guarded : rc;
+}
+
+int LastAppend(mi_devop* h, mi_devop_append* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastAppend p = h->dev.last_append();
+    out->path = p.path;
+    out->rows = p.rows;
+    out->entries = p.entries;
+    out->bytes_up = p.bytes_up;
+    out->move_shapes = p.move_shapes;
+    out->reserved = 0;
+    out->device_ms = p.device_ms;
+  });
+}
+
 static_assert(int{MI_DEVOP_TRI_UPPER} == static_cast<int>(milp::TriKind::kUpper) &&
                   int{MI_DEVOP_TRI_UNIT_ROW} == static_cast<int>(milp::TriKind::kUnitRow) &&
                   int{MI_DEVOP_TRI_UPPER_T_UP} == static_cast<int>(milp::TriKind::kUpperTUp),
@@ -1058,4 +1116,10 @@ extern "C" const mi_devop_api mi_devop_table = {
     TriAsyncFinish,   TriAsyncDrop,
     TriHostSolve,     LastTri,
     LastTriLevelWidths,
+};
+
+extern "C" const mi_devop_matrix_api mi_devop_matrix_table = {
+    AppendRows,
+    FetchMatrix,
+    LastAppend,
 };

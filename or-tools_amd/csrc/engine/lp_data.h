@@ -459,6 +459,65 @@ struct SparseColumn {
   }
 };
 
+// Rows given as lists (mi_lp_add_rows): row j holds (cols[p], vals[p]) for p in
+// [row_starts[j], row_starts[j + 1]). Valid lists start at 0, do not decrease,
+// and hold per row strictly ascending columns of [0, n) with finite non-zero
+// coefficients.
+inline bool ValidRowLists(int n, int k, const int64_t* row_starts, const int32_t* cols,
+                          const double* vals) {
+  if (k < 0 || row_starts[0] != 0) return false;
+  for (int j = 0; j < k; ++j) {
+    if (row_starts[j + 1] < row_starts[j]) return false;
+    for (int64_t p = row_starts[j]; p < row_starts[j + 1]; ++p) {
+      if (cols[p] < 0 || cols[p] >= n) return false;
+      if (p > row_starts[j] && cols[p] <= cols[p - 1]) return false;
+      if (!(vals[p] != 0.0) || !IsFinite(vals[p])) return false;
+    }
+  }
+  return true;
+}
+
+// Appends k rows (valid lists) to a CSC in place: the rows first_row + j go to
+// the ends of the first n columns, the columns [n, total_cols) behind them move
+// back by all e new entries. Columns are shifted back to front, so an entry is
+// read before its place is written; the new entries of a column land in
+// ascending row order. One pass over the columns and one over the entries.
+inline void AppendRowsToCsc(int n, int total_cols, int first_row, int k,
+                            const int64_t* row_starts, const int32_t* cols, const double* vals,
+                            std::vector<int64_t>* starts, std::vector<int>* rows,
+                            std::vector<Fractional>* coefs) {
+  const int64_t e = row_starts[k];
+  const int64_t old_total = (*starts)[total_cols];
+  std::vector<int64_t> cursor(n, 0);  // first the new entries per column
+  for (int64_t p = 0; p < e; ++p) ++cursor[cols[p]];
+  rows->resize(old_total + e);
+  coefs->resize(old_total + e);
+  int64_t shift = e;
+  int64_t old_end = old_total;
+  (*starts)[total_cols] = old_total + e;
+  for (int c = total_cols - 1; c >= 0; --c) {
+    const int64_t s = (*starts)[c];
+    const int64_t len = old_end - s;
+    if (c < n) shift -= cursor[c];
+    if (shift > 0 && len > 0) {
+      std::copy_backward(rows->begin() + s, rows->begin() + old_end,
+                         rows->begin() + old_end + shift);
+      std::copy_backward(coefs->begin() + s, coefs->begin() + old_end,
+                         coefs->begin() + old_end + shift);
+    }
+    (*starts)[c] = s + shift;
+    if (c < n) cursor[c] = s + shift + len;  // now where its next new entry goes
+    old_end = s;
+  }
+  for (int j = 0; j < k; ++j) {
+    for (int64_t p = row_starts[j]; p < row_starts[j + 1]; ++p) {
+      const int64_t at = cursor[cols[p]]++;
+      (*rows)[at] = first_row + j;
+      (*coefs)[at] = vals[p];
+    }
+  }
+}
+
 // lp_data/sparse.h:291-512 CompactSparseMatrix.
 class CompactSparseMatrix {
  public:
@@ -521,6 +580,41 @@ class CompactSparseMatrix {
         rows_[index] = col;
       }
     }
+  }
+  // This matrix is [A | I] with n structural columns: k rows (valid lists,
+  // ValidRowLists) are appended in place. The structural columns take their
+  // new entries at their ends, the old slacks keep their indices and move
+  // back, and k unit slack columns follow them. The result is what
+  // PopulateFromSparseMatrixAndAddSlacks builds from the extended A.
+  void AppendRows(int n, int k, const int64_t* row_starts, const int32_t* cols,
+                  const double* vals) {
+    const int m = num_rows_;
+    AppendRowsToCsc(n, num_cols_, m, k, row_starts, cols, vals, &starts_, &rows_,
+                    &coefficients_);
+    for (int j = 0; j < k; ++j) {
+      rows_.push_back(m + j);
+      coefficients_.push_back(1.0);
+      starts_.push_back(static_cast<int64_t>(rows_.size()));
+    }
+    num_rows_ += k;
+    num_cols_ += k;
+  }
+  // This matrix is the transpose of [A | I] (PopulateFromTranspose): the same
+  // k rows become k columns behind the others, each ending in its slack entry.
+  void AppendTransposedRows(int k, const int64_t* row_starts, const int32_t* cols,
+                            const double* vals) {
+    const int first_slack = num_rows_;  // n + m before the append
+    for (int j = 0; j < k; ++j) {
+      for (int64_t p = row_starts[j]; p < row_starts[j + 1]; ++p) {
+        rows_.push_back(cols[p]);
+        coefficients_.push_back(vals[p]);
+      }
+      rows_.push_back(first_slack + j);
+      coefficients_.push_back(1.0);
+      starts_.push_back(static_cast<int64_t>(rows_.size()));
+    }
+    num_cols_ += k;
+    num_rows_ += k;
   }
   // Columns [c0, c1) of input as a matrix of their own (a column shard of
   // [A | I] for DeviceLp's split over several devices).

@@ -3338,6 +3338,35 @@ class RevisedSimplex {
     solution_state_ = s;
     solution_state_has_been_set_externally_ = true;
   }
+  // The caller's LP was replaced (mi_lp_load): compact_matrix_ is no longer
+  // known to be its [A | I] until the next Initialize has compared them.
+  void NotifyThatLpWasLoaded() { matrix_is_the_lps_ = false; }
+  // k rows (valid lists) were appended to the caller's LP. Where
+  // compact_matrix_ is that LP's [A | I] and is on the device, the host pair
+  // and the device are extended in place, and the next Initialize takes that
+  // as what InitializeMatrixAndTestIfUnchanged would have found (the old part
+  // unchanged, new rows only), without the compare, the rebuild or the
+  // upload. num_rows_ stays that of the last solve until then: a load in
+  // between is compared against it, as after a load of the extended LP.
+  // Returns false (nothing done, the next Initialize compares and rebuilds)
+  // where there is no such matrix yet.
+  bool AppendRows(int k, const int64_t* row_starts, const int32_t* cols, const double* vals) {
+    if (!matrix_is_the_lps_ || !device_matrix_uploaded_ || transposed_matrix_.IsEmpty() ||
+        k == 0) {
+      return false;
+    }
+    compact_matrix_.AppendRows(first_slack_col_, k, row_starts, cols, vals);
+    transposed_matrix_.AppendTransposedRows(k, row_starts, cols, vals);
+    device_matrix_uploaded_ = false;  // until AppendRows on the device went through
+    try {
+      device_.AppendRows(compact_matrix_, transposed_matrix_, k);
+    } catch (...) {
+      matrix_is_the_lps_ = false;  // the next Initialize rebuilds from the LP
+      throw;
+    }
+    device_matrix_uploaded_ = true;
+    return true;
+  }
   void NotifyThatMatrixIsUnchangedForNextSolve() { notify_that_matrix_is_unchanged_ = true; }
   // revised_simplex.cc:135-137
   void NotifyThatMatrixIsChangedForNextSolve() { notify_that_matrix_is_unchanged_ = false; }
@@ -3632,6 +3661,12 @@ class RevisedSimplex {
   std::vector<Fractional> variable_starting_values_;
   std::vector<Fractional> integrality_scale_;  // SetIntegralityScale
   bool notify_that_matrix_is_unchanged_ = false;
+  // compact_matrix_ is [A | I] of the LP the caller holds (set by Initialize's
+  // compare, kept by AppendRows, dropped by NotifyThatLpWasLoaded). With it,
+  // compact_matrix_ having more rows than num_rows_ means rows were appended
+  // since the last solve; without it, that they are left over from an append
+  // that a load has overtaken.
+  bool matrix_is_the_lps_ = false;
   ScatteredVector direction_;
   Fractional direction_infinity_norm_ = 0.0;
   std::vector<Fractional> error_;
@@ -4154,8 +4189,17 @@ bool RevisedSimplex::InitializeMatrixAndTestIfUnchanged(const LinearProgram& lp,
     }
   }
   const int lp_first_slack = lp.n;
+  matrix_is_the_lps_ = true;  // on every way out of here
   if (old_part_of_matrix_is_unchanged && lp.m == num_rows_ &&
       lp_first_slack == first_slack_col_) {
+    if (compact_matrix_.num_rows() != num_rows_) {
+      // Rows appended since the last solve, then a load of the LP without
+      // them: the compare above saw the old part only.
+      compact_matrix_.PopulateFromSparseMatrixAndAddSlacks(lp.m, lp.n, lp.col_starts.data(),
+                                                           lp.row_idx.data(), lp.vals.data());
+      transposed_matrix_.PopulateFromTranspose(compact_matrix_);
+      device_matrix_uploaded_ = false;
+    }
     if (transposed_matrix_.IsEmpty()) {
       transposed_matrix_.PopulateFromTranspose(compact_matrix_);
       device_matrix_uploaded_ = false;
@@ -4358,7 +4402,17 @@ Status RevisedSimplex::Initialize(const LinearProgram& lp) {
   bool only_change_is_new_cols = false;
   bool matrix_is_unchanged = true;
   bool only_new_bounds = false;
-  if (solution_state_.empty() || !notify_that_matrix_is_unchanged_) {
+  const bool rows_differ = compact_matrix_.num_rows() != num_rows_;
+  if (rows_differ && matrix_is_the_lps_) {
+    // AppendRows extended the matrices on the host and on the device: what
+    // InitializeMatrixAndTestIfUnchanged finds for the extended LP, with the
+    // compare, the rebuild and the upload already done. A notification that
+    // the matrix is unchanged does not hold for an append.
+    matrix_is_unchanged = false;
+    only_change_is_new_rows = true;
+    num_rows_ = lp.m;
+    num_cols_ = first_slack_col_ + lp.m;
+  } else if (solution_state_.empty() || !notify_that_matrix_is_unchanged_ || rows_differ) {
     matrix_is_unchanged = InitializeMatrixAndTestIfUnchanged(
         lp, &only_change_is_new_rows, &only_change_is_new_cols, &num_new_cols);
     only_new_bounds = only_change_is_new_cols && num_new_cols > 0 &&
@@ -6097,6 +6151,24 @@ int mi_lp_load(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t*
 }  // extern "C"
 
 namespace {
+// 64-bit multiply-xor over the matrix words (a few GB/s; once per load).
+uint64_t MatrixFingerprint(const milp::LinearProgram& lp) {
+  uint64_t f = 0x243f6a8885a308d3ull ^
+               (static_cast<uint64_t>(lp.m) << 32 | static_cast<uint32_t>(lp.n));
+  auto mix = [&f](uint64_t v) {
+    f ^= v + 0x9e3779b97f4a7c15ull + (f << 6) + (f >> 2);
+    f *= 0xff51afd7ed558ccdull;
+  };
+  for (const int64_t v : lp.col_starts) mix(static_cast<uint64_t>(v));
+  const int64_t nnz = lp.col_starts[lp.n];
+  for (int64_t k = 0; k < nnz; ++k) {
+    uint64_t bits;
+    std::memcpy(&bits, &lp.vals[k], 8);
+    mix(bits ^ (static_cast<uint64_t>(static_cast<uint32_t>(lp.row_idx[k])) << 1));
+  }
+  return f;
+}
+
 int LoadLp(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t* ri,
            const double* vals, const double* clb, const double* cub, const double* rlb,
            const double* rub, const double* obj, double obj_offset, double obj_scale,
@@ -6117,23 +6189,69 @@ int LoadLp(mi_lp* h, int32_t m, int32_t n, const int64_t* cs, const int32_t* ri,
   lp.obj_offset = obj_offset;
   lp.obj_scale = obj_scale;
   lp.maximize = maximize != 0;
-  {
-    // 64-bit multiply-xor over the matrix words (a few GB/s; once per load).
-    uint64_t f = 0x243f6a8885a308d3ull ^ (static_cast<uint64_t>(m) << 32 | static_cast<uint32_t>(n));
-    auto mix = [&f](uint64_t v) {
-      f ^= v + 0x9e3779b97f4a7c15ull + (f << 6) + (f >> 2);
-      f *= 0xff51afd7ed558ccdull;
-    };
-    for (const int64_t v : lp.col_starts) mix(static_cast<uint64_t>(v));
-    for (int64_t k = 0; k < nnz; ++k) {
-      uint64_t bits;
-      std::memcpy(&bits, &lp.vals[k], 8);
-      mix(bits ^ (static_cast<uint64_t>(static_cast<uint32_t>(lp.row_idx[k])) << 1));
-    }
-    lp.matrix_fingerprint = f;
-  }
+  lp.matrix_fingerprint = MatrixFingerprint(lp);
+  h->simplex.NotifyThatLpWasLoaded();
   h->loaded = true;
   h->solved = false;
+  return MI_LP_OK;
+}
+
+// What mi_lp_load forgets: the stores hold rows and columns of the LP before.
+void ForgetStores(mi_lp* h) {
+  h->sparse_rows_stored = false;  // mi_lp_get_sparse_rows: rows of the LP before
+  h->violated_rows_stored = false;  // mi_lp_get_violated_rows: likewise
+  h->infeasible_rows_stored = false;  // mi_lp_get_infeasible_rows: likewise
+  h->tightened_columns_stored = false;  // mi_lp_get_tightened_columns: likewise
+  h->propagated_columns_stored = false;  // mi_lp_get_propagated_columns: likewise
+  h->cut_rows_stored = false;  // mi_lp_get_cut_rows: likewise
+}
+
+int AddRows(mi_lp* h, int32_t k, const int64_t* row_starts, const int32_t* cols,
+            const double* vals, const double* row_lb, const double* row_ub,
+            mi_lp_append_info* info) {
+  milp::LinearProgram& lp = h->lp;
+  if (k < 0 || !milp::ValidRowLists(lp.n, k, row_starts, cols, vals)) {
+    return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  for (int j = 0; j < k; ++j) {
+    if (std::isnan(row_lb[j]) || std::isnan(row_ub[j])) return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  const int64_t e = row_starts[k];
+  const int64_t nnz = lp.col_starts[lp.n];
+  // Rows and slack columns are int32 (n + m + k columns of [A | I]), entries
+  // int64.
+  if (int64_t(lp.n) + lp.m + k > std::numeric_limits<int32_t>::max() ||
+      e > std::numeric_limits<int64_t>::max() - nnz - lp.m - k) {
+    return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  // Everything that can fail for want of memory comes before the first
+  // change, so that an error leaves the handle as it was.
+  lp.row_idx.reserve(nnz + e);
+  lp.vals.reserve(nnz + e);
+  lp.row_lb.reserve(lp.m + k);
+  lp.row_ub.reserve(lp.m + k);
+  int path = 0;
+  (void)hipSetDevice(h->device);
+  if (h->simplex.AppendRows(k, row_starts, cols, vals)) {
+    path = h->simplex.device().last_append().path;
+  }
+  milp::AppendRowsToCsc(lp.n, lp.n, lp.m, k, row_starts, cols, vals, &lp.col_starts,
+                        &lp.row_idx, &lp.vals);
+  lp.row_lb.insert(lp.row_lb.end(), row_lb, row_lb + k);
+  lp.row_ub.insert(lp.row_ub.end(), row_ub, row_ub + k);
+  lp.m += k;
+  // The hash of the extended LP as a load computes it: one pass over all of A
+  // on the host (a few GB/s), the one part of the call that grows with nnz
+  // besides the shift of the host columns.
+  lp.matrix_fingerprint = MatrixFingerprint(lp);
+  ForgetStores(h);
+  h->solved = false;
+  if (info != nullptr) {
+    info->path = path;
+    info->rows = k;
+    info->entries = e;
+    info->bytes_up = path == 0 ? 0 : h->simplex.device().last_append().bytes_up;
+  }
   return MI_LP_OK;
 }
 // No begun solve, or one that is parked (paused or finished): its state may
@@ -6162,6 +6280,28 @@ int PanelCall(mi_lp* h, Call call) {
 }  // namespace
 
 extern "C" {
+
+int mi_lp_add_rows(mi_lp* h, int32_t k, const int64_t* row_starts, const int32_t* cols,
+                   const double* vals, const double* row_lb, const double* row_ub,
+                   mi_lp_append_info* info) {
+  if (h == nullptr || row_starts == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->loaded || h->running) return MI_LP_ERROR_STATE;
+  if (k < 0 || row_starts[0] != 0) return MI_LP_ERROR_INVALID_PROBLEM;
+  for (int j = 0; j < k; ++j) {
+    if (row_starts[j + 1] < row_starts[j]) return MI_LP_ERROR_INVALID_PROBLEM;
+  }
+  if (row_starts[k] > 0 && (cols == nullptr || vals == nullptr)) return MI_LP_ERROR_NULL;
+  if (k > 0 && (row_lb == nullptr || row_ub == nullptr)) return MI_LP_ERROR_NULL;
+  try {
+    return AddRows(h, k, row_starts, cols, vals, row_lb, row_ub, info);
+  } catch (const milp::DeviceError& e) {
+    h->error = std::string("mi_lp_add_rows: ") + e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = std::string("mi_lp_add_rows: ") + e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+}
 
 int mi_lp_load_basis_state(mi_lp* h, const int8_t* st, int32_t len) {
   if (h == nullptr || (st == nullptr && len > 0)) return MI_LP_ERROR_NULL;

@@ -735,9 +735,43 @@ struct DenseTailArgs {
   int t;
   int* fail;              // host-visible: a wait ran out
 };
+
+// Rows appended to the resident [A | I] (matrix_kernels.hip). The k new rows
+// are the tail of the new CSR: row j holds t_cols / t_vals at [tail_starts[j],
+// tail_starts[j + 1]), its structural columns ascending and its slack entry
+// last. The old CSC (n structural columns, m slacks, nnz entries) is merged
+// into freshly allocated arrays of nnz + e + k entries; e = the structural
+// entries of the tail.
+constexpr int kAppendThreads = 256;
+constexpr int kAppendTileColumns = 256;  // columns per tile of the offsets scan
+constexpr int kAppendShortColumn = 32;   // longer columns move on a workgroup
+struct MatrixAppendArgs {
+  int n, m, k;
+  int64_t nnz, e;
+  const int64_t* tail_starts;  // k + 1: t_starts[m ..] of the new CSR
+  const int32_t* t_cols;       // the new CSR's arrays
+  const double* t_vals;
+  const int64_t* old_starts;   // n + m + 1
+  const int32_t* old_rows;
+  const double* old_vals;
+  int64_t* new_starts;         // n + m + k + 1
+  int32_t* new_rows;
+  double* new_vals;
+  int* add;                    // n: new entries per column (zeroed by the caller)
+  int* rank;                   // e + k: earlier new rows that hold the entry's column
+  int tiles;                   // ceil((n + 1) / kAppendTileColumns)
+  int* tile_counts;            // tiles
+  int64_t* tile_offsets;       // tiles
+};
 }  // namespace milp_kernels
 
 namespace milp_launch {
+// The merge of MatrixAppendArgs in stream order: rank and count, tile counts,
+// tile offsets, starts, then the moves (short columns one per thread; with
+// long_columns also one workgroup per column longer than kAppendShortColumn)
+// and the scatter of the new entries and slacks.
+hipError_t matrix_append_rows(const milp_kernels::MatrixAppendArgs& args, bool long_columns,
+                              hipStream_t s);
 hipError_t column_dot(int mode, bool wave_per_col, const milp_kernels::DotArgs& args,
                       hipStream_t s);
 // unroll: 16-byte loads in flight per lane (8, 16 or 32).

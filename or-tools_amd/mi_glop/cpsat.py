@@ -470,6 +470,35 @@ def gomory_cuts(constraint, x, cols, zero_tolerance=PENALTY_PIVOT_TOLERANCE,
     return out
 
 
+def cut_rows(cuts):
+    """gomory_cuts' dicts as LpHandle.add_rows' arguments: (row_starts, cols,
+    vals, row_lb, row_ub), cut j being sum coefs * x_lp[cols] >= rhs, i.e.
+    row_lb = rhs and row_ub = +inf, at the LP's scale."""
+    starts = np.zeros(len(cuts) + 1, np.int64)
+    np.cumsum([len(c["cols"]) for c in cuts], out=starts[1:])
+    cols = np.concatenate([np.asarray(c["cols"], np.int32) for c in cuts]) if cuts \
+        else np.zeros(0, np.int32)
+    vals = np.concatenate([np.asarray(c["coefs"], np.float64) for c in cuts]) if cuts \
+        else np.zeros(0, np.float64)
+    row_lb = np.array([c["rhs"] for c in cuts], np.float64)
+    return starts, cols, vals, row_lb, np.full(len(cuts), np.inf)
+
+
+def add_cuts(constraint, cuts):
+    """Appends gomory_cuts' cuts to the constraint's LP on its handle
+    (handle.add_rows: merged into the resident matrix on the GPU) and to
+    constraint.lp_data; without scaling constraint.lp is that same LP. The
+    next solve_lp re-solves warm from the node's basis. Returns add_rows'
+    info."""
+    args = cut_rows(cuts)
+    info = constraint.h.add_rows(*args)
+    unscaled = constraint.lp_data is constraint.lp
+    constraint.lp_data = constraint.lp_data.with_rows(*args)
+    if unscaled:
+        constraint.lp = constraint.lp_data
+    return info
+
+
 def tightened_overrides(result):
     """LpHandle.tightened_columns(_from)'s result (col_starts, cols, new_lbs,
     new_ubs, summaries) as overrides[j] = (cols, new_lbs, new_ubs), one per

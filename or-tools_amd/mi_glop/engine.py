@@ -89,6 +89,8 @@ def lib():
     L.mi_lp_set_params.argtypes = [vp, ctypes.POINTER(abi.MiGlopParams)]
     L.mi_lp_load.argtypes = [vp, ctypes.c_int32, ctypes.c_int32] + [vp] * 8 + \
         [ctypes.c_double, ctypes.c_double, ctypes.c_int32]
+    L.mi_lp_add_rows.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, vp,
+                                 ctypes.POINTER(abi.MiLpAppendInfo)]
     L.mi_lp_load_basis_state.argtypes = [vp, vp, ctypes.c_int32]
     L.mi_lp_clear_basis_state.argtypes = [vp]
     L.mi_lp_notify_matrix_unchanged.argtypes = [vp]
@@ -343,6 +345,29 @@ class LpHandle:
                                        _p(clb), _p(cub), _p(rlb), _p(rub), _p(ob),
                                        lp.obj_offset, lp.obj_scale, int(lp.maximize)),
                     "mi_lp_load")
+
+    def add_rows(self, row_starts, cols, vals, row_lb, row_ub):
+        """Appends k rows given as lists to the loaded LP (include/mi_lp.h
+        mi_lp_add_rows): in every later result it is load(lp.with_rows(...)),
+        but only the new rows go to the device, where they are merged into the
+        resident matrix. Returns {"path", "rows", "entries", "bytes_up"};
+        self.lp becomes the extended LP."""
+        rs = np.ascontiguousarray(row_starts, dtype=np.int64)
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        v = np.ascontiguousarray(vals, dtype=np.float64)
+        lb = np.ascontiguousarray(row_lb, dtype=np.float64)
+        ub = np.ascontiguousarray(row_ub, dtype=np.float64)
+        k = len(rs) - 1
+        if k < 0 or len(lb) != k or len(ub) != k or len(c) != len(v) or rs[-1] != len(c):
+            raise ValueError("row_starts, cols / vals and the bounds do not describe k rows")
+        info = abi.MiLpAppendInfo()
+        self._check(self._L.mi_lp_add_rows(
+            self.h, k, _p(rs), _p(c) if len(c) else None, _p(v) if len(v) else None,
+            _p(lb) if k else None, _p(ub) if k else None, ctypes.byref(info)), "mi_lp_add_rows")
+        if self.lp is not None:
+            self.lp = self.lp.with_rows(rs, c, v, lb, ub)
+        return {"path": info.path, "rows": info.rows, "entries": info.entries,
+                "bytes_up": info.bytes_up}
 
     def solve_lp(self, lp, solver_params=None, interrupt=None):
         """glop::LPSolver::SolveWithTimeLimit on this handle (mi_lp_solver_solve):

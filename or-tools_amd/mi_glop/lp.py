@@ -51,6 +51,31 @@ class LinearProgram:
                 return False
         return bool(np.all(np.isfinite(self.obj)))
 
+    def with_rows(self, row_starts, cols, vals, row_lb, row_ub):
+        """The LP extended by k rows given as lists (LpHandle.add_rows'
+        arguments): row j, columns cols[row_starts[j]:row_starts[j+1]]
+        ascending, becomes row m + j; every column keeps its entries and takes
+        the new ones at its end. Bounds, objective and sense are shared."""
+        row_starts = np.asarray(row_starts, np.int64)
+        cols = np.asarray(cols, np.int64)
+        vals = np.asarray(vals, np.float64)
+        k = len(row_starts) - 1
+        new_rows = self.m + np.repeat(np.arange(k, dtype=np.int64), np.diff(row_starts))
+        old_cols = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(self.col_starts))
+        all_cols = np.concatenate([old_cols, cols])
+        all_rows = np.concatenate([self.row_idx.astype(np.int64), new_rows])
+        # Old entries are column-major already and every new row lies below
+        # them, so a stable sort by column alone leaves the rows ascending.
+        order = np.argsort(all_cols, kind="stable")
+        starts = np.zeros(self.n + 1, np.int64)
+        np.cumsum(np.bincount(all_cols, minlength=self.n), out=starts[1:])
+        return LinearProgram(
+            self.m + k, self.n, starts, all_rows[order].astype(np.int32),
+            np.concatenate([self.vals, vals])[order], self.col_lb, self.col_ub,
+            np.concatenate([self.row_lb, np.asarray(row_lb, np.float64)]),
+            np.concatenate([self.row_ub, np.asarray(row_ub, np.float64)]), self.obj,
+            self.obj_offset, self.obj_scale, self.maximize, self.name)
+
     @staticmethod
     def from_dense(A, col_lb, col_ub, row_lb, row_ub, obj, offset=0.0,
                    maximize=False, name="lp"):
