@@ -270,6 +270,59 @@ int mi_lp_add_rows(mi_lp* h, int32_t k, const int64_t* row_starts, const int32_t
                    const double* vals, const double* row_lb, const double* row_ub,
                    mi_lp_append_info* info /* may be NULL */);
 
+/* Deletes rows from the loaded LP (the cuts a cut loop purges, CP-SAT's
+ * LinearConstraintManager::ChangeLp over glop's LinearProgram::DeleteRows).
+ * delete_mask has m bytes; a non-zero byte deletes its row. Kept rows keep
+ * their order: row r becomes row r - (deleted rows below r) and its slack
+ * column n + that index; the slack columns of deleted rows disappear;
+ * structural columns keep their indices.
+ *
+ * The contract: in any sequence of calls on a handle, mi_lp_delete_rows(mask)
+ * may be replaced by (1) mi_lp_load of the reduced LP (the same columns with
+ * the deleted rows' entries removed and the rows renumbered, the kept row
+ * bounds, and the handle's current column bounds, objective, offset, scale
+ * and sense) and (2), only if the state the next solve would start from (the
+ * last solve's final state, or the one given to mi_lp_load_basis_state since)
+ * is non-empty and has n + m entries, mi_lp_load_basis_state of that state
+ * with the entries n + r of the deleted rows removed; a state of another
+ * length, or none, means (1) alone. No bit of anything the handle later
+ * returns changes: solve results, iterations, basis, state and rays, every
+ * panel call (refused until the next solve, as after a load),
+ * mi_lp_batch_solve_bounds (the matrix fingerprint is that of the load) and
+ * the stores of the mi_lp_get_* lists (forgotten, as on a load).
+ * mi_lp_set_starting_variable_values is left as the load leaves it. That
+ * holds before a first solve, after mi_lp_load_basis_state, for two deletes
+ * in a row, for a delete after an append (of exactly the appended rows too),
+ * for an append after a delete (of as many rows too), and for a mi_lp_load
+ * between the delete and the solve. Only the time and the bytes moved
+ * differ: where the handle's matrix is resident on the device, only the mask
+ * crosses PCIe, the resident CSC and CSR are compacted on the device, and the
+ * next solve starts without the entry-by-entry compare, the host rebuild or
+ * the upload (it refactorizes, as glop does). The host still compacts its own
+ * columns and re-hashes A (one pass each), and until the next solve it keeps
+ * a copy of the last solve's matrix if one of that solve's rows went. One
+ * exception to the contract: after mi_lp_notify_matrix_unchanged the load
+ * twin would solve on the stale matrix; the delete is honoured instead.
+ *
+ * A mask with no row set succeeds and is the load of the same LP, with (2)
+ * still applied. A mask that deletes every row is the load of the LP with
+ * m = 0; it takes the full upload (path 2), never the compaction.
+ *
+ *   MI_LP_ERROR_NULL   h NULL, or delete_mask NULL with m > 0
+ *   MI_LP_ERROR_STATE  before mi_lp_load, or while a begun solve runs
+ * There is no MI_LP_ERROR_INVALID_PROBLEM case. On every error nothing
+ * changes, neither on the host nor on the device. */
+typedef struct mi_lp_delete_info {
+  int32_t path;      /* 0: no device matrix yet (host only); 1: compacted on the
+                        device; 2: full upload from the reduced host matrices
+                        (column shards, or no row kept) */
+  int32_t rows;      /* d = deleted rows */
+  int64_t entries;   /* structural entries removed */
+  int64_t bytes_up;  /* host -> device for the matrix: on path 1 the mask, m bytes */
+} mi_lp_delete_info;
+int mi_lp_delete_rows(mi_lp* h, const uint8_t* delete_mask /* m; non-zero deletes */,
+                      mi_lp_delete_info* info /* may be NULL */);
+
 /* statuses: n+m glop::VariableStatus values (structural then slacks). */
 int mi_lp_load_basis_state(mi_lp* h, const int8_t* statuses, int32_t len);
 int mi_lp_clear_basis_state(mi_lp* h);

@@ -558,6 +558,31 @@ typedef struct mi_devop_matrix_api {
 
 extern const mi_devop_matrix_api mi_devop_matrix_table;
 
+/* DeviceLp::LastDelete: the last delete_rows. The shapes are MI_DEVOP_MOVE_*
+ * bits, per thread and per workgroup, for the CSC columns and the CSR rows. */
+typedef struct mi_devop_delete {
+  int32_t path;          /* 1 compacted on the device, 2 full upload */
+  int32_t rows;          /* deleted rows */
+  int64_t entries;       /* structural entries removed */
+  int64_t bytes_up;      /* host -> device for the matrix */
+  int32_t column_shapes; /* of the count and move kernels that ran for columns */
+  int32_t row_shapes;    /* of the move kernels that ran for rows */
+  double device_ms;      /* the mask's copy and the kernels, by events */
+} mi_devop_delete;
+
+/* Row deletion, in a third table: mi_devop_matrix_delete_table. */
+typedef struct mi_devop_matrix_delete_api {
+  /* The rows of delete_mask (m bytes, non-zero deletes; include/mi_lp.h
+   * mi_lp_delete_rows) leave the handle's csc / csr on the host
+   * (CompactSparseMatrix::DeleteRows, DeleteTransposedRows) and the device
+   * with DeviceLp::DeleteRows. The relevant mask the handle remembers is all
+   * ones afterwards, as after create. */
+  int (*delete_rows)(mi_devop* h, const uint8_t* delete_mask);
+  int (*last_delete)(mi_devop* h, mi_devop_delete* out);
+} mi_devop_matrix_delete_api;
+
+extern const mi_devop_matrix_delete_api mi_devop_matrix_delete_table;
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,26 @@ class DeviceLp : public DeviceSolver {
     double device_ms = 0.0;  // copies and merge kernels, by events
   };
   LastAppend last_append() const { return last_append_; }
+  // (csc, csr) are the resident pair with the rows of delete_mask (the
+  // resident m bytes, non-zero deletes) removed on the host
+  // (CompactSparseMatrix::DeleteRows / DeleteTransposedRows). Only the mask is
+  // uploaded and nothing comes back: the CSC and the CSR are compacted on the
+  // device (matrix_kernels.hip) into new arrays, and every buffer sized by
+  // (m, N) is re-made, so that the members equal what UploadMatrix(csc, csr)
+  // leaves. Old and new matrix arrays coexist for the length of the call. With
+  // column shards, or with no row kept, it is UploadMatrix(csc, csr).
+  void DeleteRows(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr,
+                  const uint8_t* delete_mask);
+  struct LastDelete {
+    int path = 0;           // 1 compacted on the device, 2 full upload
+    int rows = 0;           // deleted rows
+    int64_t entries = 0;    // structural entries removed
+    int64_t bytes_up = 0;   // host -> device for the matrix
+    int column_shapes = 0;  // bit 0: column per thread ran, bit 1: column per workgroup
+    int row_shapes = 0;     // the same for the CSR rows
+    double device_ms = 0.0;  // the mask's copy and the kernels, by events
+  };
+  LastDelete last_delete() const { return last_delete_; }
   // The resident matrix as the device holds it (test support; not on a
   // solve's path): CSC, CSR, the dense column list and the dense block (body,
   // then tail, as BuildDenseBlock packs them).
@@ -954,6 +974,7 @@ class DeviceLp : public DeviceSolver {
   void SetMatrixShape(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr);
   void AllocateForShape();
   LastAppend last_append_;
+  LastDelete last_delete_;
   // Launches the CSC kernel over the sparse columns (all columns when there is
   // no dense block) and the dense-block kernel; mode as in column_dot.
   void LaunchColumnDots(int mode, const double* d_y, const double* d_c, double* d_out,

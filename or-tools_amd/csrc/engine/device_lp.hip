@@ -1036,6 +1036,112 @@ void DeviceLp::AppendRows(const CompactSparseMatrix& csc, const CompactSparseMat
   Synchronize();
 }
 
+void DeviceLp::DeleteRows(const CompactSparseMatrix& csc, const CompactSparseMatrix& csr,
+                          const uint8_t* delete_mask) {
+  last_delete_ = LastDelete{};
+  const int old_m = m_;
+  const int n = n_total_ - m_;
+  const int64_t old_nnz = nnz_;
+  const int kept = csc.num_rows();
+  if (kept > old_m || csc.num_cols() != n + kept || csr.num_cols() != kept ||
+      csc.num_entries() != csr.num_entries() || csc.num_entries() > old_nnz - (old_m - kept)) {
+    throw DeviceError("DeleteRows: the reduced matrices do not reduce the resident one");
+  }
+  last_delete_.rows = old_m - kept;
+  last_delete_.entries = old_nnz - csc.num_entries() - (old_m - kept);
+  if (!shards_.empty() || kept == 0) {
+    // Column shards hold slices of their own, and a matrix without rows is
+    // the upload's case: the existing upload from the reduced pair.
+    UploadMatrix(csc, csr);
+    last_delete_.path = 2;
+    last_delete_.bytes_up = (csc.num_cols() + 1 + csr.num_cols() + 1) * int64_t(sizeof(int64_t)) +
+                            2 * csc.num_entries() * int64_t(sizeof(int32_t) + sizeof(double));
+    return;
+  }
+  Check(hipSetDevice(device_), "hipSetDevice");
+  SetStreamPriority(stream_priority_);
+  if (batch_pending_) WaitSmallBatch();
+  Check(hipStreamSynchronize(S(stream_)), "sync");
+  // The old matrix stays until the compaction is done; everything else sized
+  // by the old shape goes first.
+  int64_t* old_starts = d_starts_;
+  int32_t* old_rows = d_rows_;
+  double* old_vals = d_vals_;
+  int64_t* old_t_starts = d_t_starts_;
+  int32_t* old_t_cols = d_t_cols_;
+  double* old_t_vals = d_t_vals_;
+  void* const keep[6] = {old_starts, old_rows, old_vals, old_t_starts, old_t_cols, old_t_vals};
+  for (void* p : allocations_) {
+    if (std::find(keep, keep + 6, p) == keep + 6) (void)hipFree(p);
+  }
+  allocations_.assign(keep, keep + 6);
+  bool long_columns = false;  // of the old structural columns, which are what is read
+  for (int c = 0; c < n && !long_columns; ++c) {
+    long_columns = h_starts_[c + 1] - h_starts_[c] > milp_kernels::kDeleteShort;
+  }
+  bool long_rows = false;  // of the kept rows, whose lengths the delete leaves
+  for (int r = 0; r < kept && !long_rows; ++r) {
+    long_rows = csr.starts_[r + 1] - csr.starts_[r] > milp_kernels::kDeleteShort;
+  }
+  SetMatrixShape(csc, csr);
+  d_starts_ = Alloc<int64_t>(n_total_ + 1);
+  d_rows_ = Alloc<int32_t>(nnz_);
+  d_vals_ = Alloc<double>(nnz_);
+  d_t_starts_ = Alloc<int64_t>(m_ + 1);
+  d_t_cols_ = Alloc<int32_t>(nnz_);
+  d_t_vals_ = Alloc<double>(nnz_);
+  milp_kernels::MatrixDeleteArgs a{};
+  a.n = n;
+  a.m = old_m;
+  a.kept = kept;
+  a.new_structural = csc.starts_[n];
+  a.row_tiles = (old_m + milp_kernels::kDeleteTile - 1) / milp_kernels::kDeleteTile;
+  a.col_tiles = (n + milp_kernels::kDeleteTile - 1) / milp_kernels::kDeleteTile;
+  uint8_t* d_mask = Alloc<uint8_t>(old_m);
+  a.delete_mask = d_mask;
+  a.new_row = Alloc<int>(old_m);
+  a.count = Alloc<int>(n);
+  a.row_tile_rows = Alloc<int>(a.row_tiles);
+  a.row_tile_entries = Alloc<int64_t>(a.row_tiles);
+  a.col_tile_entries = Alloc<int64_t>(a.col_tiles);
+  a.old_starts = old_starts;
+  a.old_rows = old_rows;
+  a.old_vals = old_vals;
+  a.old_t_starts = old_t_starts;
+  a.old_t_cols = old_t_cols;
+  a.old_t_vals = old_t_vals;
+  a.new_starts = d_starts_;
+  a.new_rows = d_rows_;
+  a.new_vals = d_vals_;
+  a.new_t_starts = d_t_starts_;
+  a.new_t_cols = d_t_cols_;
+  a.new_t_vals = d_t_vals_;
+  hipEvent_t ev0 = reinterpret_cast<hipEvent_t>(ev_start_);
+  hipEvent_t ev1 = reinterpret_cast<hipEvent_t>(ev_stop_);
+  Check(hipEventRecord(ev0, S(stream_)), "event");
+  Upload(d_mask, delete_mask, old_m * sizeof(uint8_t));  // all that goes up
+  last_delete_.bytes_up = old_m;
+  Check(milp_launch::matrix_delete_rows(a, long_columns, long_rows, S(stream_)), "delete rows");
+  Check(hipEventRecord(ev1, S(stream_)), "event");
+  Check(hipStreamSynchronize(S(stream_)), "sync");  // also: the upload reads pageable memory
+  float ms = 0.0f;
+  Check(hipEventElapsedTime(&ms, ev0, ev1), "elapsed");
+  last_delete_.device_ms = ms;
+  last_delete_.path = 1;
+  last_delete_.column_shapes = n > 0 ? (long_columns ? 3 : 1) : 0;
+  last_delete_.row_shapes = long_rows ? 3 : 1;
+  // The old matrix and the compaction's scratch go; the six new arrays stay,
+  // in UploadMatrix's order.
+  void* const now[6] = {d_starts_, d_rows_, d_vals_, d_t_starts_, d_t_cols_, d_t_vals_};
+  for (void* p : allocations_) {
+    if (std::find(now, now + 6, p) == now + 6) (void)hipFree(p);
+  }
+  allocations_.assign(now, now + 6);
+  AllocateForShape();
+  BuildDenseBlock();
+  Synchronize();
+}
+
 void DeviceLp::FetchMatrix(MatrixCopy* out) {
   Check(hipSetDevice(device_), "hipSetDevice");
   Synchronize();

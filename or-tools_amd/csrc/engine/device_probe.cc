@@ -1046,6 +1046,32 @@ int LastAppend(mi_devop* h, mi_devop_append* out) {
   });
 }
 
+int DeleteRows(mi_devop* h, const uint8_t* delete_mask) {
+  return Guard(h, [&] {
+    const int m = h->csc.num_rows();
+    const int n = h->csc.num_cols() - m;
+    if (delete_mask == nullptr && m > 0) throw milp::DeviceError("delete_rows: no mask");
+    const std::vector<int> new_row = milp::NewRowIndices(m, delete_mask);
+    h->csc.DeleteRows(n, delete_mask, new_row.data());
+    h->csr.DeleteTransposedRows(n, delete_mask, new_row.data());
+    h->dev.DeleteRows(h->csc, h->csr, delete_mask);
+    h->relevant.assign((h->csc.num_cols() + 63) / 64, ~0ull);
+  });
+}
+
+int LastDelete(mi_devop* h, mi_devop_delete* out) {
+  return Guard(h, [&] {
+    const milp::DeviceLp::LastDelete p = h->dev.last_delete();
+    out->path = p.path;
+    out->rows = p.rows;
+    out->entries = p.entries;
+    out->bytes_up = p.bytes_up;
+    out->column_shapes = p.column_shapes;
+    out->row_shapes = p.row_shapes;
+    out->device_ms = p.device_ms;
+  });
+}
+
 static_assert(int{MI_DEVOP_TRI_UPPER} == static_cast<int>(milp::TriKind::kUpper) &&
                   int{MI_DEVOP_TRI_UNIT_ROW} == static_cast<int>(milp::TriKind::kUnitRow) &&
                   int{MI_DEVOP_TRI_UPPER_T_UP} == static_cast<int>(milp::TriKind::kUpperTUp),
@@ -1122,4 +1148,9 @@ extern "C" const mi_devop_matrix_api mi_devop_matrix_table = {
     AppendRows,
     FetchMatrix,
     LastAppend,
+};
+
+extern "C" const mi_devop_matrix_delete_api mi_devop_matrix_delete_table = {
+    DeleteRows,
+    LastDelete,
 };

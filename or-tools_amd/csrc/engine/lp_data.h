@@ -518,6 +518,47 @@ inline void AppendRowsToCsc(int n, int total_cols, int first_row, int k,
   }
 }
 
+// Deletes rows from a CSC of `cols` columns in place (mi_lp_delete_rows):
+// delete_mask has num_rows bytes, non-zero deletes; new_row[r] is the index a
+// kept row r takes (the kept rows below it). Compacts front to back: an entry
+// is written at or before the place it is read from. Kept entries keep their
+// order, so the rows of a column stay ascending. Returns the entries left.
+inline int64_t DeleteRowsFromCsc(int cols, const uint8_t* delete_mask, const int* new_row,
+                                 std::vector<int64_t>* starts, std::vector<int>* rows,
+                                 std::vector<Fractional>* coefs) {
+  int64_t out = 0;
+  int64_t begin = (*starts)[0];
+  for (int c = 0; c < cols; ++c) {
+    const int64_t end = (*starts)[c + 1];
+    (*starts)[c] = out;
+    for (int64_t p = begin; p < end; ++p) {
+      const int r = (*rows)[p];
+      if (delete_mask[r] != 0) continue;
+      (*rows)[out] = new_row[r];
+      (*coefs)[out] = (*coefs)[p];
+      ++out;
+    }
+    begin = end;
+  }
+  (*starts)[cols] = out;
+  rows->resize(out);
+  coefs->resize(out);
+  return out;
+}
+
+// new_row[r] = the rows r' < r that the mask keeps, for r in [0, m]; new_row[m]
+// is the number of kept rows.
+inline std::vector<int> NewRowIndices(int m, const uint8_t* delete_mask) {
+  std::vector<int> new_row(m + 1);
+  int kept = 0;
+  for (int r = 0; r < m; ++r) {
+    new_row[r] = kept;
+    kept += delete_mask[r] == 0 ? 1 : 0;
+  }
+  new_row[m] = kept;
+  return new_row;
+}
+
 // lp_data/sparse.h:291-512 CompactSparseMatrix.
 class CompactSparseMatrix {
  public:
@@ -615,6 +656,54 @@ class CompactSparseMatrix {
     }
     num_cols_ += k;
     num_rows_ += k;
+  }
+  // This matrix is [A | I] with n structural columns: the rows the mask names
+  // (num_rows() bytes, non-zero deletes; new_row from NewRowIndices) are
+  // deleted in place. Kept rows keep their order and are renumbered, the
+  // structural columns keep their indices, the slack columns of deleted rows
+  // disappear. The result is what PopulateFromSparseMatrixAndAddSlacks builds
+  // from the reduced A. Returns the structural entries removed.
+  int64_t DeleteRows(int n, const uint8_t* delete_mask, const int* new_row) {
+    const int m = num_rows_;
+    const int kept = new_row[m];
+    const int64_t before = num_entries();
+    DeleteRowsFromCsc(num_cols_, delete_mask, new_row, &starts_, &rows_, &coefficients_);
+    // A deleted row's slack column is empty now; the kept ones close ranks.
+    for (int r = 0; r < m; ++r) {
+      if (delete_mask[r] == 0) starts_[n + new_row[r]] = starts_[n + r];
+    }
+    starts_[n + kept] = num_entries();
+    starts_.resize(n + kept + 1);
+    num_rows_ = kept;
+    num_cols_ = n + kept;
+    return before - num_entries() - (m - kept);
+  }
+  // This matrix is the transpose of [A | I] (PopulateFromTranspose) with n
+  // structural columns: the same rows, which are columns here, go. A kept
+  // row moves to the front with its entries as they are, but for its last
+  // one, the slack, which becomes n + new_row[r].
+  void DeleteTransposedRows(int n, const uint8_t* delete_mask, const int* new_row) {
+    const int m = num_cols_;
+    const int kept = new_row[m];
+    int64_t out = 0;
+    for (int r = 0; r < m; ++r) {
+      const int64_t begin = starts_[r];
+      const int64_t end = starts_[r + 1];
+      if (delete_mask[r] != 0) continue;
+      starts_[new_row[r]] = out;
+      for (int64_t p = begin; p < end; ++p) {
+        rows_[out] = rows_[p];
+        coefficients_[out] = coefficients_[p];
+        ++out;
+      }
+      rows_[out - 1] = n + new_row[r];
+    }
+    starts_[kept] = out;
+    starts_.resize(kept + 1);
+    rows_.resize(out);
+    coefficients_.resize(out);
+    num_cols_ = kept;
+    num_rows_ = n + kept;
   }
   // Columns [c0, c1) of input as a matrix of their own (a column shard of
   // [A | I] for DeviceLp's split over several devices).

@@ -3355,6 +3355,11 @@ class RevisedSimplex {
         k == 0) {
       return false;
     }
+    // Set before the first change: if the device call throws, the host pair
+    // is already extended, and the flag is what makes the next Initialize
+    // compare and rebuild from the LP (also after a notification that the
+    // matrix is unchanged).
+    matrix_edited_since_solve_ = true;
     compact_matrix_.AppendRows(first_slack_col_, k, row_starts, cols, vals);
     transposed_matrix_.AppendTransposedRows(k, row_starts, cols, vals);
     device_matrix_uploaded_ = false;  // until AppendRows on the device went through
@@ -3366,6 +3371,57 @@ class RevisedSimplex {
     }
     device_matrix_uploaded_ = true;
     return true;
+  }
+  // The rows of delete_mask (lp_m bytes, non-zero deletes; `deleted` of them)
+  // leave the caller's LP of lp_n columns. Where compact_matrix_ is that LP's
+  // [A | I] and is on the device, the host pair and the device are compacted
+  // in place (*edited = true; otherwise the next Initialize compares and
+  // rebuilds); with no row kept the device takes the full upload. The first delete since the last solve
+  // that reaches a row of that solve keeps a copy of the matrix as it was:
+  // the next Initialize, or a load's compare, decides against it what
+  // InitializeMatrixAndTestIfUnchanged would have found for the reduced LP.
+  // Then the state the next solve would start from, if it has lp_n + lp_m
+  // entries, is loaded without the deleted rows' slacks
+  // (LoadStateForNextSolve). What can fail for want of memory comes first.
+  void DeleteRows(const uint8_t* delete_mask, int lp_m, int lp_n, int deleted, bool* edited) {
+    *edited = false;
+    const std::vector<int> new_row = NewRowIndices(lp_m, delete_mask);
+    std::vector<VariableStatus> state;
+    const bool edit_state = !solution_state_.empty() &&
+                            static_cast<int64_t>(solution_state_.size()) == int64_t(lp_n) + lp_m;
+    if (edit_state) {
+      state.reserve(lp_n + lp_m - deleted);
+      state.assign(solution_state_.begin(), solution_state_.begin() + lp_n);
+      for (int r = 0; r < lp_m; ++r) {
+        if (delete_mask[r] == 0) state.push_back(solution_state_[lp_n + r]);
+      }
+    }
+    if (matrix_is_the_lps_ && device_matrix_uploaded_ && !transposed_matrix_.IsEmpty() &&
+        deleted > 0 && compact_matrix_.num_rows() == lp_m &&
+        first_slack_col_ == lp_n) {
+      bool reaches_solved_rows = false;
+      for (int r = 0; r < std::min(lp_m, num_rows_) && !reaches_solved_rows; ++r) {
+        reaches_solved_rows = delete_mask[r] != 0;
+      }
+      if (reaches_solved_rows && !solved_rows_deleted_) matrix_at_last_solve_ = compact_matrix_;
+      solved_rows_deleted_ = solved_rows_deleted_ || reaches_solved_rows;
+      matrix_edited_since_solve_ = true;
+      compact_matrix_.DeleteRows(lp_n, delete_mask, new_row.data());
+      transposed_matrix_.DeleteTransposedRows(lp_n, delete_mask, new_row.data());
+      device_matrix_uploaded_ = false;  // until DeleteRows on the device went through
+      try {
+        device_.DeleteRows(compact_matrix_, transposed_matrix_, delete_mask);
+      } catch (...) {
+        matrix_is_the_lps_ = false;  // the next Initialize rebuilds from the LP
+        throw;
+      }
+      device_matrix_uploaded_ = true;
+      *edited = true;
+    }
+    if (edit_state) {  // LoadStateForNextSolve(state), without its copy
+      solution_state_.swap(state);
+      solution_state_has_been_set_externally_ = true;
+    }
   }
   void NotifyThatMatrixIsUnchangedForNextSolve() { notify_that_matrix_is_unchanged_ = true; }
   // revised_simplex.cc:135-137
@@ -3445,6 +3501,7 @@ class RevisedSimplex {
     update_row_.SetParameters(parameters_);
   }
   Status Initialize(const LinearProgram& lp);
+  bool OldPartOfMatrixIsUnchanged(const LinearProgram& lp, const CompactSparseMatrix& last) const;
   bool InitializeMatrixAndTestIfUnchanged(const LinearProgram& lp,
                                           bool* only_change_is_new_rows,
                                           bool* only_change_is_new_cols,
@@ -3662,11 +3719,19 @@ class RevisedSimplex {
   std::vector<Fractional> integrality_scale_;  // SetIntegralityScale
   bool notify_that_matrix_is_unchanged_ = false;
   // compact_matrix_ is [A | I] of the LP the caller holds (set by Initialize's
-  // compare, kept by AppendRows, dropped by NotifyThatLpWasLoaded). With it,
-  // compact_matrix_ having more rows than num_rows_ means rows were appended
-  // since the last solve; without it, that they are left over from an append
-  // that a load has overtaken.
+  // compare, kept by AppendRows and DeleteRows, dropped by
+  // NotifyThatLpWasLoaded).
   bool matrix_is_the_lps_ = false;
+  // AppendRows or DeleteRows changed compact_matrix_ since the last Initialize
+  // (rows can come and go, so the row counts do not tell). With
+  // matrix_is_the_lps_ the edits are the LP's; without it they are left over
+  // from edits that a load has overtaken, and the matrix is rebuilt.
+  bool matrix_edited_since_solve_ = false;
+  // A delete since the last Initialize reached a row below num_rows_:
+  // matrix_at_last_solve_ is compact_matrix_ as it was before the first such
+  // delete, the one the compare of a load twin would run against.
+  bool solved_rows_deleted_ = false;
+  CompactSparseMatrix matrix_at_last_solve_;
   ScatteredVector direction_;
   Fractional direction_infinity_norm_ = 0.0;
   std::vector<Fractional> error_;
@@ -4160,41 +4225,46 @@ void RevisedSimplex::UseSingletonColumnInInitialBasis(std::vector<int>* basis) {
   }
 }
 
+// lp_data/matrix_utils.cc AreFirstColumnsAndRowsExactlyEquals over the last
+// solve's num_rows_ x first_slack_col_: `last` is the matrix of that solve,
+// possibly with rows appended behind it since (AppendRows), which do not
+// count.
+bool RevisedSimplex::OldPartOfMatrixIsUnchanged(const LinearProgram& lp,
+                                                const CompactSparseMatrix& last) const {
+  const int nr = num_rows_;
+  const int nc = first_slack_col_;
+  if (nr > lp.m || nr > last.num_rows() || nc > lp.n || nc > last.num_cols()) return false;
+  for (int col = 0; col < nc; ++col) {
+    const int64_t a0 = lp.col_starts[col];
+    const int64_t na = lp.col_starts[col + 1] - a0;
+    const ColumnView b = last.column(col);
+    int64_t bn = b.n;
+    while (bn > 0 && b.rows[bn - 1] >= nr) --bn;
+    const int64_t end = std::min(na, bn);
+    if (end < na && lp.row_idx[a0 + end] < nr) return false;
+    if (end < bn && b.rows[end] < nr) return false;
+    for (int64_t i = 0; i < end; ++i) {
+      if (lp.row_idx[a0 + i] != b.rows[i] || lp.vals[a0 + i] != b.coefs[i]) return false;
+    }
+  }
+  return true;
+}
+
 // revised_simplex.cc:928-1002 + lp_data/matrix_utils.cc
 // AreFirstColumnsAndRowsExactlyEquals.
 bool RevisedSimplex::InitializeMatrixAndTestIfUnchanged(const LinearProgram& lp,
                                                         bool* only_change_is_new_rows,
                                                         bool* only_change_is_new_cols,
                                                         int* num_new_cols) {
-  bool old_part_of_matrix_is_unchanged = true;
-  {
-    const int nr = num_rows_;
-    const int nc = first_slack_col_;
-    if (nr > lp.m || nr > compact_matrix_.num_rows() || nc > lp.n ||
-        nc > compact_matrix_.num_cols()) {
-      old_part_of_matrix_is_unchanged = false;
-    } else {
-      for (int col = 0; col < nc && old_part_of_matrix_is_unchanged; ++col) {
-        const int64_t a0 = lp.col_starts[col];
-        const int64_t na = lp.col_starts[col + 1] - a0;
-        const ColumnView b = compact_matrix_.column(col);
-        const int64_t end = std::min(na, b.n);
-        if (end < na && lp.row_idx[a0 + end] < nr) old_part_of_matrix_is_unchanged = false;
-        if (end < b.n && b.rows[end] < nr) old_part_of_matrix_is_unchanged = false;
-        for (int64_t i = 0; i < end && old_part_of_matrix_is_unchanged; ++i) {
-          if (lp.row_idx[a0 + i] != b.rows[i] || lp.vals[a0 + i] != b.coefs[i])
-            old_part_of_matrix_is_unchanged = false;
-        }
-      }
-    }
-  }
+  const bool old_part_of_matrix_is_unchanged = OldPartOfMatrixIsUnchanged(
+      lp, solved_rows_deleted_ ? matrix_at_last_solve_ : compact_matrix_);
   const int lp_first_slack = lp.n;
   matrix_is_the_lps_ = true;  // on every way out of here
   if (old_part_of_matrix_is_unchanged && lp.m == num_rows_ &&
       lp_first_slack == first_slack_col_) {
-    if (compact_matrix_.num_rows() != num_rows_) {
-      // Rows appended since the last solve, then a load of the LP without
-      // them: the compare above saw the old part only.
+    if (matrix_edited_since_solve_) {
+      // Rows appended or deleted since the last solve, then a load of an LP
+      // that has the last solve's rows: the compare saw those only.
       compact_matrix_.PopulateFromSparseMatrixAndAddSlacks(lp.m, lp.n, lp.col_starts.data(),
                                                            lp.row_idx.data(), lp.vals.data());
       transposed_matrix_.PopulateFromTranspose(compact_matrix_);
@@ -4402,22 +4472,33 @@ Status RevisedSimplex::Initialize(const LinearProgram& lp) {
   bool only_change_is_new_cols = false;
   bool matrix_is_unchanged = true;
   bool only_new_bounds = false;
-  const bool rows_differ = compact_matrix_.num_rows() != num_rows_;
-  if (rows_differ && matrix_is_the_lps_) {
-    // AppendRows extended the matrices on the host and on the device: what
-    // InitializeMatrixAndTestIfUnchanged finds for the extended LP, with the
-    // compare, the rebuild and the upload already done. A notification that
-    // the matrix is unchanged does not hold for an append.
-    matrix_is_unchanged = false;
-    only_change_is_new_rows = true;
-    num_rows_ = lp.m;
-    num_cols_ = first_slack_col_ + lp.m;
-  } else if (solution_state_.empty() || !notify_that_matrix_is_unchanged_ || rows_differ) {
+  if (matrix_edited_since_solve_ && matrix_is_the_lps_) {
+    // AppendRows and DeleteRows edited the matrices on the host and on the
+    // device: what InitializeMatrixAndTestIfUnchanged finds for the edited LP,
+    // with the rebuild and the upload already done. Appends, and deletes of
+    // rows appended since the last solve, leave that solve's part as it was.
+    // A delete that reached it leaves fewer rows than the solve had, which
+    // that compare takes as changed at once; only where appends have made up
+    // for them does the compare run, against the matrix kept for it. A
+    // notification that the matrix is unchanged does not hold for an edit.
+    const bool old_part_of_matrix_is_unchanged =
+        !solved_rows_deleted_ || OldPartOfMatrixIsUnchanged(lp, matrix_at_last_solve_);
+    if (!old_part_of_matrix_is_unchanged || lp.m != num_rows_) {
+      matrix_is_unchanged = false;
+      only_change_is_new_rows = old_part_of_matrix_is_unchanged && lp.m > num_rows_;
+      num_rows_ = lp.m;
+      num_cols_ = first_slack_col_ + lp.m;
+    }
+  } else if (solution_state_.empty() || !notify_that_matrix_is_unchanged_ ||
+             matrix_edited_since_solve_) {
     matrix_is_unchanged = InitializeMatrixAndTestIfUnchanged(
         lp, &only_change_is_new_rows, &only_change_is_new_cols, &num_new_cols);
     only_new_bounds = only_change_is_new_cols && num_new_cols > 0 &&
                       OldBoundsAreUnchangedAndNewVariablesHaveOneBoundAtZero(lp, num_new_cols);
   }
+  matrix_edited_since_solve_ = false;
+  solved_rows_deleted_ = false;
+  matrix_at_last_solve_ = CompactSparseMatrix();
   notify_that_matrix_is_unchanged_ = false;
   const bool objective_is_unchanged = InitializeObjectiveAndTestIfUnchanged(lp);
   const bool bounds_are_unchanged = variables_info_.LoadBoundsAndReturnTrueIfUnchanged(
@@ -6234,6 +6315,11 @@ int AddRows(mi_lp* h, int32_t k, const int64_t* row_starts, const int32_t* cols,
   (void)hipSetDevice(h->device);
   if (h->simplex.AppendRows(k, row_starts, cols, vals)) {
     path = h->simplex.device().last_append().path;
+  } else if (k > 0) {
+    // The solver's matrix does not follow (there is none on the device, or
+    // none with rows): the next solve compares and rebuilds, whatever edits
+    // went before.
+    h->simplex.NotifyThatLpWasLoaded();
   }
   milp::AppendRowsToCsc(lp.n, lp.n, lp.m, k, row_starts, cols, vals, &lp.col_starts,
                         &lp.row_idx, &lp.vals);
@@ -6251,6 +6337,45 @@ int AddRows(mi_lp* h, int32_t k, const int64_t* row_starts, const int32_t* cols,
     info->rows = k;
     info->entries = e;
     info->bytes_up = path == 0 ? 0 : h->simplex.device().last_append().bytes_up;
+  }
+  return MI_LP_OK;
+}
+int DeleteRows(mi_lp* h, const uint8_t* delete_mask, mi_lp_delete_info* info) {
+  milp::LinearProgram& lp = h->lp;
+  // Everything that can fail for want of memory comes before the first
+  // change (here the row map, in RevisedSimplex::DeleteRows the state and the
+  // copy of the last solve's matrix); compacting allocates nothing.
+  const std::vector<int> new_row = milp::NewRowIndices(lp.m, delete_mask);
+  const int deleted = lp.m - new_row[lp.m];
+  const int64_t nnz = lp.col_starts[lp.n];
+  bool edited = false;
+  (void)hipSetDevice(h->device);
+  h->simplex.DeleteRows(delete_mask, lp.m, lp.n, deleted, &edited);
+  // Without a device matrix the next solve compares and uploads as after a
+  // load.
+  if (!edited && deleted > 0) h->simplex.NotifyThatLpWasLoaded();
+  if (deleted > 0) {
+    milp::DeleteRowsFromCsc(lp.n, delete_mask, new_row.data(), &lp.col_starts, &lp.row_idx,
+                            &lp.vals);
+    for (int r = 0; r < lp.m; ++r) {
+      if (delete_mask[r] != 0) continue;
+      lp.row_lb[new_row[r]] = lp.row_lb[r];
+      lp.row_ub[new_row[r]] = lp.row_ub[r];
+    }
+    lp.m -= deleted;
+    lp.row_lb.resize(lp.m);
+    lp.row_ub.resize(lp.m);
+  }
+  // The hash of the reduced LP as a load computes it: one pass over A on the
+  // host, with the column shift the part of the call that grows with nnz.
+  lp.matrix_fingerprint = MatrixFingerprint(lp);
+  ForgetStores(h);
+  h->solved = false;
+  if (info != nullptr) {
+    info->path = edited ? h->simplex.device().last_delete().path : 0;
+    info->rows = deleted;
+    info->entries = nnz - lp.col_starts[lp.n];
+    info->bytes_up = edited ? h->simplex.device().last_delete().bytes_up : 0;
   }
   return MI_LP_OK;
 }
@@ -6299,6 +6424,21 @@ int mi_lp_add_rows(mi_lp* h, int32_t k, const int64_t* row_starts, const int32_t
     return MI_LP_ERROR_DEVICE;
   } catch (const std::exception& e) {
     h->error = std::string("mi_lp_add_rows: ") + e.what();
+    return MI_LP_ERROR_INTERNAL;
+  }
+}
+
+int mi_lp_delete_rows(mi_lp* h, const uint8_t* delete_mask, mi_lp_delete_info* info) {
+  if (h == nullptr) return MI_LP_ERROR_NULL;
+  if (!h->loaded || h->running) return MI_LP_ERROR_STATE;
+  if (delete_mask == nullptr && h->lp.m > 0) return MI_LP_ERROR_NULL;
+  try {
+    return DeleteRows(h, delete_mask, info);
+  } catch (const milp::DeviceError& e) {
+    h->error = std::string("mi_lp_delete_rows: ") + e.what();
+    return MI_LP_ERROR_DEVICE;
+  } catch (const std::exception& e) {
+    h->error = std::string("mi_lp_delete_rows: ") + e.what();
     return MI_LP_ERROR_INTERNAL;
   }
 }

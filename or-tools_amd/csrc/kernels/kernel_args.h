@@ -763,6 +763,38 @@ struct MatrixAppendArgs {
   int* tile_counts;            // tiles
   int64_t* tile_offsets;       // tiles
 };
+
+// Rows deleted from the resident [A | I] (matrix_kernels.hip). delete_mask has
+// m bytes, non-zero deletes the row (the mask of mi_lp_delete_rows as it is).
+// The old CSC (n structural columns, m slacks) and CSR are compacted into
+// freshly allocated arrays; the host knows the new shape from its own
+// compacted pair: kept rows and the structural entries left.
+constexpr int kDeleteThreads = 256;
+constexpr int kDeleteTile = 256;         // rows or columns per tile of the scans
+constexpr int kDeleteShort = 32;         // longer columns / rows move on a workgroup
+struct MatrixDeleteArgs {
+  int n, m, kept;
+  int64_t new_structural;      // entries of the new structural columns
+  const uint8_t* delete_mask;  // m
+  const int64_t* old_starts;   // n + m + 1
+  const int32_t* old_rows;
+  const double* old_vals;
+  const int64_t* old_t_starts; // m + 1
+  const int32_t* old_t_cols;
+  const double* old_t_vals;
+  int64_t* new_starts;         // n + kept + 1
+  int32_t* new_rows;
+  double* new_vals;
+  int64_t* new_t_starts;       // kept + 1
+  int32_t* new_t_cols;
+  double* new_t_vals;
+  int* new_row;                // m: the kept rows below r
+  int* count;                  // n: kept entries per structural column
+  int row_tiles, col_tiles;    // ceil(m / kDeleteTile), ceil(n / kDeleteTile)
+  int* row_tile_rows;          // row_tiles: kept rows of the tile, then those before it
+  int64_t* row_tile_entries;   // row_tiles: their CSR entries, likewise
+  int64_t* col_tile_entries;   // col_tiles: kept entries of the tile, then before it
+};
 }  // namespace milp_kernels
 
 namespace milp_launch {
@@ -772,6 +804,14 @@ namespace milp_launch {
 // and the scatter of the new entries and slacks.
 hipError_t matrix_append_rows(const milp_kernels::MatrixAppendArgs& args, bool long_columns,
                               hipStream_t s);
+// The compaction of MatrixDeleteArgs in stream order: the row map and the new
+// CSR starts (count per tile, one workgroup over the tile counts, starts per
+// tile), the CSR moves, the kept entries per column, the CSC starts by the
+// same three passes, the CSC moves and the slack columns. long_rows /
+// long_columns: some kept row / old structural column is longer than
+// kDeleteShort and the workgroup kernels run as well.
+hipError_t matrix_delete_rows(const milp_kernels::MatrixDeleteArgs& args, bool long_columns,
+                              bool long_rows, hipStream_t s);
 hipError_t column_dot(int mode, bool wave_per_col, const milp_kernels::DotArgs& args,
                       hipStream_t s);
 // unroll: 16-byte loads in flight per lane (8, 16 or 32).

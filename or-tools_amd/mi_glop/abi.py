@@ -166,6 +166,16 @@ class MiLpAppendInfo(ctypes.Structure):
     ]
 
 
+class MiLpDeleteInfo(ctypes.Structure):
+    """mi_lp_delete_info (include/mi_lp.h): what mi_lp_delete_rows did."""
+    _fields_ = [
+        ("path", ctypes.c_int32),
+        ("rows", ctypes.c_int32),
+        ("entries", ctypes.c_int64),
+        ("bytes_up", ctypes.c_int64),
+    ]
+
+
 KERNEL_NAMES = ["pricing", "update_row", "primal_norms", "rc_update", "tri_solve",
                 "col_norms", "spmv_rows", "single_row", "dual_ratio", "readback",
                 "tri_solve_tau", "tri_solve_l", "tri_solve_t", "tri_solve_upper", "sdual",
@@ -175,6 +185,7 @@ KERNEL_NAMES = ["pricing", "update_row", "primal_norms", "rc_update", "tri_solve
 EXPORTED_SYMBOLS = [
     "mi_glop_params_default", "mi_lp_device_count", "mi_lp_shutdown", "mi_lp_create",
     "mi_lp_destroy", "mi_lp_last_error", "mi_lp_set_params", "mi_lp_load", "mi_lp_add_rows",
+    "mi_lp_delete_rows",
     "mi_lp_load_basis_state", "mi_lp_clear_basis_state",
     "mi_lp_notify_matrix_unchanged", "mi_lp_solve", "mi_lp_get_primal",
     "mi_lp_get_reduced_costs", "mi_lp_get_duals", "mi_lp_get_activities",

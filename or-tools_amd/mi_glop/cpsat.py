@@ -499,6 +499,26 @@ def add_cuts(constraint, cuts):
     return info
 
 
+def purge_cuts(constraint, first_cut_row):
+    """Deletes every row at or above first_cut_row whose slack is BASIC in the
+    handle's state (the rule of LinearConstraintManager::ChangeLp: a cut that
+    is not tight after the re-solve goes) from the constraint's LP on its
+    handle (handle.delete_rows: the resident matrix is compacted on the GPU
+    and the state loses those slacks) and from constraint.lp_data; without
+    scaling constraint.lp is that same LP. Returns (deleted row indices,
+    delete_rows' info)."""
+    h = constraint.h
+    n, m = h.lp.n, h.lp.m
+    mask = np.zeros(m, bool)
+    mask[first_cut_row:] = h.state()[n + first_cut_row:] == BASIC
+    info = h.delete_rows(mask)
+    unscaled = constraint.lp_data is constraint.lp
+    constraint.lp_data = constraint.lp_data.without_rows(mask)
+    if unscaled:
+        constraint.lp = constraint.lp_data
+    return np.flatnonzero(mask), info
+
+
 def tightened_overrides(result):
     """LpHandle.tightened_columns(_from)'s result (col_starts, cols, new_lbs,
     new_ubs, summaries) as overrides[j] = (cols, new_lbs, new_ubs), one per

@@ -91,6 +91,7 @@ def lib():
         [ctypes.c_double, ctypes.c_double, ctypes.c_int32]
     L.mi_lp_add_rows.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, vp,
                                  ctypes.POINTER(abi.MiLpAppendInfo)]
+    L.mi_lp_delete_rows.argtypes = [vp, vp, ctypes.POINTER(abi.MiLpDeleteInfo)]
     L.mi_lp_load_basis_state.argtypes = [vp, vp, ctypes.c_int32]
     L.mi_lp_clear_basis_state.argtypes = [vp]
     L.mi_lp_notify_matrix_unchanged.argtypes = [vp]
@@ -366,6 +367,38 @@ class LpHandle:
             _p(lb) if k else None, _p(ub) if k else None, ctypes.byref(info)), "mi_lp_add_rows")
         if self.lp is not None:
             self.lp = self.lp.with_rows(rs, c, v, lb, ub)
+        return {"path": info.path, "rows": info.rows, "entries": info.entries,
+                "bytes_up": info.bytes_up}
+
+    def delete_rows(self, rows):
+        """Deletes rows from the loaded LP (include/mi_lp.h mi_lp_delete_rows):
+        `rows` is a boolean mask of length m or an array of row indices (out of
+        range or repeated: ValueError). In every later result it is
+        load(lp.without_rows(mask)) followed by load_basis_state of the state
+        without the deleted rows' slacks, but only the mask goes to the
+        device, where the resident matrix is compacted. Returns {"path",
+        "rows", "entries", "bytes_up"}; self.lp becomes the reduced LP."""
+        m = self.lp.m
+        r = np.asarray(rows)
+        if r.dtype == np.bool_:
+            if r.shape != (m,):
+                raise ValueError("a row mask has one entry per row")
+            mask = r
+        else:
+            if r.size and not np.issubdtype(r.dtype, np.integer):
+                raise ValueError("row indices are integers (or pass a boolean mask)")
+            idx = r.astype(np.int64).reshape(-1)
+            if len(idx) and (idx.min() < 0 or idx.max() >= m):
+                raise ValueError("a row index is out of range")
+            if len(np.unique(idx)) != len(idx):
+                raise ValueError("a row index is repeated")
+            mask = np.zeros(m, bool)
+            mask[idx] = True
+        bytes_ = np.ascontiguousarray(mask, dtype=np.uint8)
+        info = abi.MiLpDeleteInfo()
+        self._check(self._L.mi_lp_delete_rows(self.h, _p(bytes_) if m else None,
+                                              ctypes.byref(info)), "mi_lp_delete_rows")
+        self.lp = self.lp.without_rows(mask)
         return {"path": info.path, "rows": info.rows, "entries": info.entries,
                 "bytes_up": info.bytes_up}
 

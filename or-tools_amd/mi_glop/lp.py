@@ -76,6 +76,24 @@ class LinearProgram:
             np.concatenate([self.row_ub, np.asarray(row_ub, np.float64)]), self.obj,
             self.obj_offset, self.obj_scale, self.maximize, self.name)
 
+    def without_rows(self, mask):
+        """The LP without the rows that the boolean mask (length m) names:
+        kept rows keep their order and are renumbered, every column keeps its
+        other entries in order. Column bounds, objective and sense are
+        shared."""
+        mask = np.asarray(mask, bool)
+        if mask.shape != (self.m,):
+            raise ValueError("a row mask has one entry per row")
+        new_row = np.cumsum(~mask) - 1
+        keep = ~mask[self.row_idx]
+        cols = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(self.col_starts))
+        starts = np.zeros(self.n + 1, np.int64)
+        np.cumsum(np.bincount(cols[keep], minlength=self.n), out=starts[1:])
+        return LinearProgram(
+            int((~mask).sum()), self.n, starts, new_row[self.row_idx[keep]].astype(np.int32),
+            self.vals[keep], self.col_lb, self.col_ub, self.row_lb[~mask], self.row_ub[~mask],
+            self.obj, self.obj_offset, self.obj_scale, self.maximize, self.name)
+
     @staticmethod
     def from_dense(A, col_lb, col_ub, row_lb, row_ub, obj, offset=0.0,
                    maximize=False, name="lp"):
